@@ -31,6 +31,13 @@ committed moves/s and says so in value_kind.
 
 --gpus N without a torch.distributed launcher starts N ranks itself (one process per
 GPU, RCCL world size N); under torchrun the environment's WORLD_SIZE is used.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) measures the headline window only:
+set-up, W warm-up steps, N timed steps, the result line.  --full adds what earlier
+versions measured by default: the CPU baseline (and the speed-ups quoted on it), a second
+window at the default (1e-3) precision beside a fast headline, and at C2 a third one on a
+trained net (--trained-steps).  --dump-outputs DIR writes the training rows the last timed
+step handed to its caller, as float32 .npy files (dump_outputs below).
 """
 import argparse
 import faulthandler
@@ -80,6 +87,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, the default-precision ('compliant') window beside a fast "
+                         "headline and, at C2, the trained-net window (--trained-steps); a plain run times the "
+                         "headline window only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's training rows (the headline window's) "
+                         "to DIR/<name>.npy as float32 and its counters as float64")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="C2")
     ap.add_argument("--games", type=int, default=0, help="games per GPU (0 = the config's)")
     ap.add_argument("--visits", type=int, default=0, help="visits per move (0 = the config's)")
@@ -92,13 +106,13 @@ def parse():
                     help="network precision of the headline window (default: fast for C2 -- fp16 operands, the "
                          "configs' fp16/bf16 dtype class, within 1e-3 of fp32 on this random-init benchmark net "
                          "(tests/test_gpu_nn.py) but not on trained nets; 'default' for C3-C5, the layered nets' "
-                         "1e-3 path.  A fast headline also measures a window at 'default', the product's "
+                         "1e-3 path.  With --full a fast headline also measures a window at 'default', the product's "
                          "1e-3 path (the C ABI's, the CLI's and the configs' precision), which the CPU speed-up "
                          "is quoted on)")
     ap.add_argument("--trained-steps", type=int, default=-1,
                     help="also measure the default precision on a trained net: one generation of the reference's "
                          "loop on this GPU (the engine's own self-play rows from the random-init net, then N Adam "
-                         "steps of katacoffee_amd.train); -1: 200 for C2, 0 otherwise; 0: skip")
+                         "steps of katacoffee_amd.train); -1: 200 for C2 with --full, 0 otherwise; 0: skip")
     # 16: a game whose search is done waits at most 15 rounds for its move, and every
     # group's round chain carries half the commit / row launches of 8 (C2: +2.4 %)
     ap.add_argument("--commit-interval", type=int, default=16)
@@ -149,8 +163,11 @@ def parse():
     args = ap.parse_args()
     if args.precision is None:
         args.precision = "fast" if args.config == "C2" else "default"
+    if not args.full:  # a plain run: the headline window alone
+        args.no_cpu_baseline = True
+        args.compliant_line = False
     if args.trained_steps < 0:
-        args.trained_steps = 200 if args.config == "C2" else 0
+        args.trained_steps = 200 if args.config == "C2" and args.full else 0
     if args.commit_interval < 1:
         ap.error("--commit-interval must be >= 1")
     if args.groups < 0 or args.steps < 1 or args.warmup < 0:
@@ -534,6 +551,35 @@ class Groups:
             e.close()
 
 
+# --dump-outputs: the float32 copies of the dumped rows stay below this many bytes
+DUMP_BYTES = 48 << 20
+# counters.npy: rows of the last step, rows dumped, then these totals of the window
+COUNTER_NAMES = ["moves", "playouts", "nn_evals"]
+
+
+def dump_outputs(outdir, rows, counters, seed, prefix=""):
+    """Writes the last timed step's training rows (`rows`: katacoffee_amd.rows.unpack of the
+    block the step staged, i.e. the arrays of the .npz row format plus the engine's meta
+    column) as outdir/<prefix><field>.npy in float32 -- every field is an integer type or
+    f32, so the copies are exact -- and `counters` (name -> number) as counters.npy in
+    float64, in the order of COUNTER_NAMES.  Rows are put in a canonical order (slot, game
+    number, turn: the device appends them in completion order); when they exceed DUMP_BYTES,
+    a sample drawn with `seed` from the ordered rows is written."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    meta = rows["meta"]
+    n = len(meta)
+    order = np.lexsort((meta[:, 3], meta[:, 2], meta[:, 1], meta[:, 0]))
+    per_row = 4 * sum(int(np.prod(a.shape[1:])) for a in rows.values())
+    cap = DUMP_BYTES // per_row
+    if n > cap:
+        order = order[np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))]
+    for name, a in rows.items():
+        np.save(os.path.join(outdir, prefix + name + ".npy"), a[order].astype(np.float32))
+    np.save(os.path.join(outdir, prefix + "counters.npy"),
+            np.array([n, len(order)] + [counters[k] for k in COUNTER_NAMES], np.float64))
+
+
 def load_traffic(path):
     try:
         return json.load(open(path))
@@ -617,9 +663,9 @@ def main():
         # profiles/r06/groups_hwqueues_ab*.txt, line_c3_4groups.json, line_c4_4groups.json);
         # b18c384nbt's forward is throughput-bound (C5: -12 % playouts/s with two)
         args.groups = 4 if cfg["arch"] != "b18c384nbt" else 1
-    def measure(precision, with_cpu, model_path=model_path):
+    def measure(precision, with_cpu, model_path=model_path, dump=None):
         """One timed window at `precision` with the network `model_path`; rank 0 returns the
-        JSON dict."""
+        JSON dict.  dump: a directory for this window's dump_outputs."""
         # nn_batch_cap 0: the engines split the fused network's one wave of workgroups
         # (engines_per_device); the layered network has no batch cap (its cost grows with the batch)
         sp = Groups(kc, args.groups, games, rank * games, chunk=args.commit_interval, X=X, Y=Y, W=W, max_visits=visits, seed=args.seed,
@@ -680,8 +726,10 @@ def main():
             # step i's rows: device block -> this rank's host -> its writer thread (local
             # sink), or -> RCCL gather to rank 0 first (gather sink), while the next step's
             # kernels run on the engine streams
-            sink.put(sp.collect(i))
+            block = sp.collect(i)
+            sink.put(block)
             torch.cuda.current_stream().synchronize()  # slot i's blocks are free for step + 2
+            return block
 
         barrier()
         t0 = time.perf_counter()
@@ -696,7 +744,7 @@ def main():
                 process(prev)
             prev = step % 2
             progress("timed", step, args.steps, t0)
-        process(prev)
+        last_block = process(prev)
         sp.sync()
         if writer:
             writer.close()  # every drained row is on disk before the clock stops
@@ -704,6 +752,9 @@ def main():
         elapsed = time.perf_counter() - t0
         s1 = sp.stats()
         d = {k: s1[k] - s0[k] for k in ("moves", "playouts", "nn_evals", "tree_levels", "tree_children")}
+        if dump:  # this rank's rows of the last step, after the clock stopped
+            dump_outputs(dump, kcrows.unpack(last_block.cpu().numpy(), X, Y), d, args.seed,
+                         prefix="rank%d_" % rank if world > 1 else "")
         kt = [sp.kernel_time(i) for i in range(5)]
         timed_evals = sp.timed_nn_evals() - base_timed_evals
         rows_gathered, npz_rows, npz_files, rank_rows = sink.totals(
@@ -854,7 +905,7 @@ def main():
         sp.close()
         return None
 
-    out = measure(args.precision, True)
+    out = measure(args.precision, True, dump=args.dump_outputs)
 
     def side_window(comp, tolerance):
         return {"precision": "default -> %s" % comp["config"]["precision"], "dtype": comp["dtype"],
@@ -898,7 +949,8 @@ def main():
         if args.precision == "fast":
             out["precision_note"] = ("headline at fp16 operands (the configs' fp16/bf16 class): within 1e-3 of fp32 on "
                                      "this random-init benchmark net (tests/test_gpu_nn.py), not on trained nets; "
-                                     "'compliant' is the product's default (1e-3) precision, the speed-up basis")
+                                     "'compliant' (--full) is the product's default (1e-3) precision, the speed-up "
+                                     "basis")
         cpu = out.get("cpu_baseline")
         if cpu and cpu["value"] > 0:
             # the product's 1e-3 path against the whole host's physical cores;

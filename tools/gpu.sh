@@ -3,7 +3,8 @@
 # call (no further GPU work after a fault, abort or timeout).  Logs go to gpurun_out/.
 #   test[=PATTERN]   pytest -m gpu (optionally -k PATTERN)
 #   file=PATH        pytest of one test file (gpu-marked tests in it)
-#   bench[=ARGS]     python bench.py ARGS (comma-separated: bench=--config,C3,--steps,10)
+#   bench[=ARGS]     python bench.py ARGS (comma-separated: bench=--config,C3,--steps,10; bench=--full adds
+#                    the CPU baseline and the default-precision and trained-net windows)
 #   benchlong[=ARGS] the same with a 1050 s limit (long-game windows: C5 rows on disk)
 #   lines            tools/bench_lines.sh (every config's bench line, gpurun_out/lines.json)
 #   smoke            __graft_entry__.smoke()

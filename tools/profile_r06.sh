@@ -60,8 +60,8 @@ for s in "$@"; do
     accpmc)
       pmc r06_c2acc_fetch FETCH_SIZE $SHORT --precision accurate
       pmc r06_c2acc_write WRITE_SIZE $SHORT --precision accurate ;;
-    main) line c2 600 --steps 20 --warmup 5 ;;
-    prodline) line c2prod 600 --steps 20 --warmup 5 --play production --no-cpu-baseline --trained-steps 0 ;;
+    main) line c2 600 --full --steps 20 --warmup 5 ;;
+    prodline) line c2prod 600 --full --steps 20 --warmup 5 --play production --no-cpu-baseline --trained-steps 0 ;;
     c3line) line c3 700 --config C3 --steps 20 --warmup 5 --no-cpu-baseline ;;
     c4line) line c4 500 --config C4 --steps 6 --warmup 5 --no-cpu-baseline ;;
     c4g4line) line c4g4 500 --config C4 --steps 6 --warmup 5 --no-cpu-baseline --groups 4 ;;
