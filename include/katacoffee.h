@@ -341,6 +341,87 @@ int coffee_selfplay_set_model(coffee_selfplay* h, const char* model_path);
 int coffee_selfplay_set_model_bytes(coffee_selfplay* h, const void* data, uint64_t bytes);
 int coffee_selfplay_destroy(coffee_selfplay* h);
 
+/* ---- two-network match play (replaces the game loop of the reference's gatekeeper,
+ *      cpp/command/gatekeeper.cpp:111-187, on the self-play engine's kernels) ----
+ * num_games concurrent games between net 0 (the baseline) and net 1 (the candidate).
+ * Colour rule: in game number n of global slot s = slot_base + slot the candidate plays
+ * black (player 1) iff s + n is even (the reference's {{0,1},{1,0}} pairing).
+ * Net choice: every evaluation a game asks for in a round -- root evaluations with their
+ * sampled symmetries, leaf evaluations, policy-init opening evaluations -- is done by the
+ * net of the ROOT player to move of that game, in that net's own launch (net 0's, then
+ * net 1's, on the engine stream), and cached in that net's own evaluation cache.
+ * Tree: cleared before every search, so no evaluation of the other net survives a move.
+ * Settings that keep a tree or exist only to make training rows are rejected with
+ * COFFEE_EINVAL before any device call: cheap_search_prob > 0, reduce_visits != 0, a fork
+ * probability > 0, side_position_prob > 0, record_tree_positions != 0, a surprise weight
+ * != 0.  init_games_with_policy stays allowed (it gives the openings their variety).
+ * As in self-play, a game's moves are chosen without LCB (use_lcb_for_selection is carried
+ * in the params and not applied to game moves).
+ * Output: finished-game records only; no training rows exist and nothing counts as dropped.
+ * The batch cap applies to both nets' rows together, with self-play's round-robin rule;
+ * the rounds always run the separate select and backup kernels (COFFEE_FUSED_ROUNDS is
+ * ignored). */
+typedef struct coffee_match_config {
+  int32_t x, y, win_len;
+  int32_t num_games;       /* concurrent games on this device (numGameThreads) */
+  int32_t node_cap;        /* per-game node pool; 0 = max(2048, 3*max_visits) */
+  uint64_t seed;
+  int32_t slot_base;       /* global index of slot 0: it enters the colour rule */
+  int32_t commit_interval; /* as coffee_selfplay_config */
+  int32_t start_stagger;   /* as coffee_selfplay_config */
+  const char* model_path[2]; /* CFNN models of net 0 (baseline) and net 1 (candidate), host
+                              strings; NULL = the stand-in network (coffee_fake_net) */
+  coffee_search_params search; /* coffee_match_params_default */
+  int32_t nn_cache_log2;   /* entries of EACH net's evaluation cache = 2^nn_cache_log2; 0 disables */
+  int32_t nn_batch_cap;    /* rows per round over both nets' launches together; 0 = the smaller
+                              of the two nets' own caps (coffee_selfplay_config.nn_batch_cap) */
+  int32_t nn_precision;    /* COFFEE_NN_*: each net resolves it on its own */
+  int32_t engines_per_device; /* as coffee_selfplay_config */
+} coffee_match_config;
+
+typedef struct coffee_match coffee_match;
+
+typedef struct coffee_match_stats {
+  uint64_t rounds;
+  uint64_t playouts;
+  uint64_t nn_evals[2];       /* network rows evaluated by net 0 / net 1 */
+  uint64_t moves;
+  uint64_t games_finished;
+  uint64_t games_dropped;     /* game records lost to a full record buffer (2 x num_games) */
+  uint64_t errors;            /* as coffee_selfplay_stats: nonzero makes stats return COFFEE_EINTERNAL */
+  uint64_t nn_precision[2];   /* the precision each net runs (0 = stand-in net) */
+  uint64_t nn_batch_peak[2];  /* the largest batch each net was given in one round */
+  /* the default precision's running audit (coffee_selfplay_stats), per net: a switch to the
+   * accurate instance affects that net, and that net's cache, only */
+  uint64_t nn_audits[2];
+  uint64_t nn_audit_switches[2];
+  double nn_audit_max_diff[2];
+} coffee_match_stats;
+
+/* The search values of configs/training/gatekeeper1.cfg (:49, :72-80, :95-106): 150 visits,
+ * move temperature 0.5 early / 0.2 with halflife 19, LCB on at 5.0 / 0.15, root FPU
+ * reduction 0.1, subtree value bias 0.35; what that config leaves at the reference's
+ * defaults: root noise off, root policy temperatures 1, no desired-per-child visits, one
+ * root symmetry.  Every play setting off.  Other fields as coffee_search_params_default. */
+void coffee_match_params_default(coffee_search_params* p);
+int coffee_match_create(const coffee_match_config* cfg, coffee_match** out);
+/* As coffee_selfplay_step / _sync / _stream / _destroy. */
+int coffee_match_step(coffee_match* h, int rounds, void* stream);
+int coffee_match_sync(coffee_match* h);
+int coffee_match_stream(coffee_match* h, void** stream);
+int coffee_match_destroy(coffee_match* h);
+int coffee_match_stats_get(coffee_match* h, coffee_match_stats* out);
+/* As coffee_selfplay_drain_games with header [g][5] i32: (slot, game number, number of
+ * moves, winner 0 draw / 1 black / 2 white, the candidate's colour 1 black / 2 white). */
+int coffee_match_drain_games(coffee_match* h, int max_games, int32_t* header, uint8_t* moves, int* n_out);
+/* Points of n drained games (header [n][5], host): a win 1, a draw 0.5 to each side. */
+int coffee_match_score(const int32_t* header, int n, double* candidate_points, double* baseline_points);
+/* The self-play inspectors' layouts (coffee_selfplay_game_info / _game_tree / _root_policy). */
+int coffee_match_game_info(coffee_match* h, int slot, int64_t* info);
+int coffee_match_game_tree(coffee_match* h, int slot, int max_nodes, uint32_t* nodes, uint32_t* edges,
+                           int* n_nodes);
+int coffee_match_root_policy(coffee_match* h, int slot, float* out);
+
 /* Writes n rows (HOST arrays, drain_rows layout) as a training .npz in the reference's
  * format (TrainingWriteBuffers::writeToZipFile trainingwrite.cpp:566-587): members
  * binaryInputNCHWPacked, globalInputNC, policyTargetsNCMove, globalTargetsNC,

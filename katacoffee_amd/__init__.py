@@ -101,6 +101,29 @@ class SelfplayStats(ctypes.Structure):
                  "nn_audit_switches"]] + [("nn_audit_max_diff", ctypes.c_double)]
 
 
+class MatchConfig(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_int32), ("y", ctypes.c_int32), ("win_len", ctypes.c_int32),
+        ("num_games", ctypes.c_int32), ("node_cap", ctypes.c_int32),
+        ("seed", ctypes.c_uint64), ("slot_base", ctypes.c_int32), ("commit_interval", ctypes.c_int32),
+        ("start_stagger", ctypes.c_int32),
+        ("model_path", ctypes.c_char_p * 2),
+        ("search", SearchParams),
+        ("nn_cache_log2", ctypes.c_int32),
+        ("nn_batch_cap", ctypes.c_int32),
+        ("nn_precision", ctypes.c_int32),
+        ("engines_per_device", ctypes.c_int32),
+    ]
+
+
+class MatchStats(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_uint64), ("playouts", ctypes.c_uint64), ("nn_evals", ctypes.c_uint64 * 2),
+                ("moves", ctypes.c_uint64), ("games_finished", ctypes.c_uint64), ("games_dropped", ctypes.c_uint64),
+                ("errors", ctypes.c_uint64), ("nn_precision", ctypes.c_uint64 * 2),
+                ("nn_batch_peak", ctypes.c_uint64 * 2), ("nn_audits", ctypes.c_uint64 * 2),
+                ("nn_audit_switches", ctypes.c_uint64 * 2), ("nn_audit_max_diff", ctypes.c_double * 2)]
+
+
 # Every symbol include/katacoffee.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "coffee_last_error", "coffee_abi_version", "coffee_device_count", "coffee_set_device", "coffee_device_compute_units", "coffee_malloc",
@@ -115,6 +138,9 @@ EXPORTS = [
     "coffee_selfplay_game_tree", "coffee_selfplay_root_policy", "coffee_debug_cdf_table", "coffee_debug_zobrist",
     "coffee_selfplay_enable_timing", "coffee_selfplay_kernel_time", "coffee_selfplay_timed_nn_evals",
     "coffee_write_npz",
+    "coffee_match_params_default", "coffee_match_create", "coffee_match_step", "coffee_match_sync",
+    "coffee_match_stream", "coffee_match_destroy", "coffee_match_stats_get", "coffee_match_drain_games",
+    "coffee_match_score", "coffee_match_game_info", "coffee_match_game_tree", "coffee_match_root_policy",
 ]
 
 
@@ -178,6 +204,19 @@ def lib():
         L.coffee_debug_cdf_table.argtypes = [c_i, c_i, c_i, c_p]
         L.coffee_debug_zobrist.argtypes = [c_i, c_i, c_i] + [c_p] * 5
         L.coffee_write_npz.argtypes = [ctypes.c_char_p, c_i, c_i, c_i] + [c_p] * 5
+        L.coffee_match_params_default.argtypes = [c_p]
+        L.coffee_match_params_default.restype = None
+        L.coffee_match_create.argtypes = [c_p, c_p]
+        L.coffee_match_step.argtypes = [c_p, c_i, c_p]
+        L.coffee_match_sync.argtypes = [c_p]
+        L.coffee_match_stream.argtypes = [c_p, c_p]
+        L.coffee_match_destroy.argtypes = [c_p]
+        L.coffee_match_stats_get.argtypes = [c_p, c_p]
+        L.coffee_match_drain_games.argtypes = [c_p, c_i, c_p, c_p, c_p]
+        L.coffee_match_score.argtypes = [c_p, c_i, c_p, c_p]
+        L.coffee_match_game_info.argtypes = [c_p, c_i, c_p]
+        L.coffee_match_game_tree.argtypes = [c_p, c_i, c_i, c_p, c_p, c_p]
+        L.coffee_match_root_policy.argtypes = [c_p, c_i, c_p]
         _lib = L
     return _lib
 
@@ -198,6 +237,24 @@ def default_search_params(**over):
     for k, v in over.items():
         setattr(p, k, v)
     return p
+
+
+def default_match_params(**over):
+    """coffee_match_params_default: gatekeeper1.cfg's search values, every play setting off."""
+    p = SearchParams()
+    lib().coffee_match_params_default(ctypes.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def match_score(header):
+    """(candidate points, baseline points) of drained match games (header [n][5]): a win 1,
+    a draw 0.5 to each side (coffee_match_score)."""
+    header = np.ascontiguousarray(header, np.int32).reshape(-1, 5)
+    c, b = ctypes.c_double(), ctypes.c_double()
+    check(lib().coffee_match_score(_ptr(header), len(header), ctypes.byref(c), ctypes.byref(b)))
+    return c.value, b.value
 
 
 # ---------------------------------------------------------------------------
@@ -545,6 +602,107 @@ class Selfplay:
     def close(self):
         if self.h:
             lib().coffee_selfplay_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Match:
+    """One device's two-network match engine (coffee_match_*): games [slot_base, slot_base +
+    num_games) between net 0 (baseline_path) and net 1 (candidate_path); None = the stand-in
+    network.  The candidate plays black in game n of global slot s iff s + n is even, and
+    every evaluation of a game in a round is done by the net of its root player.  Mirrors
+    Selfplay's stepping and inspection interface; there are no training rows.
+    search: a SearchParams to start from instead of default_match_params(); keyword
+    overrides apply on top of either."""
+
+    def __init__(self, X=5, Y=5, W=4, num_games=128, baseline_path=None, candidate_path=None, seed=1, slot_base=0,
+                 node_cap=0, commit_interval=0, nn_cache_log2=0, nn_batch_cap=0, nn_precision="default",
+                 start_stagger=0, engines_per_device=0, search=None, **search_over):
+        self.X, self.Y, self.W = X, Y, W
+        self.A, self.P = X * Y, 4 * X * Y
+        self.num_games = num_games
+        self.slot_base = slot_base
+        search = default_match_params() if search is None else SearchParams.from_buffer_copy(search)
+        for k, v in search_over.items():
+            setattr(search, k, v)
+        cfg = MatchConfig()
+        cfg.x, cfg.y, cfg.win_len = X, Y, W
+        cfg.num_games = num_games
+        cfg.node_cap = node_cap
+        cfg.seed = seed
+        cfg.slot_base = slot_base
+        cfg.commit_interval = commit_interval
+        cfg.start_stagger = start_stagger
+        self._models = [p.encode() if p else None for p in (baseline_path, candidate_path)]
+        cfg.model_path[0], cfg.model_path[1] = self._models
+        cfg.search = search
+        cfg.nn_cache_log2 = nn_cache_log2
+        cfg.nn_batch_cap = nn_batch_cap
+        cfg.nn_precision = PRECISIONS[nn_precision]
+        cfg.engines_per_device = engines_per_device
+        self.cfg = cfg
+        self.h = ctypes.c_void_p()
+        check(lib().coffee_match_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+
+    def step(self, rounds, stream=None):
+        check(lib().coffee_match_step(self.h, rounds, stream))
+
+    def sync(self):
+        check(lib().coffee_match_sync(self.h))
+
+    def stats(self):
+        s = MatchStats()
+        check(lib().coffee_match_stats_get(self.h, ctypes.byref(s)))
+        out = {}
+        for k, t in MatchStats._fields_:
+            v = getattr(s, k)
+            out[k] = list(v) if hasattr(v, "__len__") else v
+        return out
+
+    def stream_ptr(self):
+        p = ctypes.c_void_p()
+        check(lib().coffee_match_stream(self.h, ctypes.byref(p)))
+        return p.value
+
+    def drain_games(self, max_games=1 << 20):
+        """Finished-game records: header [g][5] i32 (slot, game number, moves, winner,
+        candidate's colour) and moves [g][A][2] u8 (cell, direction; 0xFF past the last move)."""
+        cap = min(max_games, 2 * self.num_games)
+        header = np.zeros((cap, 5), np.int32)
+        moves = np.zeros((cap, self.A, 2), np.uint8)
+        got = ctypes.c_int()
+        check(lib().coffee_match_drain_games(self.h, cap, _ptr(header), _ptr(moves), ctypes.byref(got)))
+        return header[:got.value], moves[:got.value]
+
+    score = staticmethod(match_score)
+
+    def game_info(self, slot):
+        info = np.zeros(16, np.int64)
+        check(lib().coffee_match_game_info(self.h, slot, _ptr(info)))
+        keys = ["phase", "rootK", "liveCount", "rootIdx", "gameNum", "turn", "pla", "finished", "winner",
+                "playouts", "nnEvals", "moves", "gamesFinished", "lastCell", "lastDir", "rngCtr"]
+        return dict(zip(keys, info.tolist()))
+
+    def game_tree(self, slot, max_nodes=4096):
+        nodes = np.zeros((max_nodes, 24), np.uint32)
+        edges = np.zeros((max_nodes, self.P, 3), np.uint32)
+        n = ctypes.c_int()
+        check(lib().coffee_match_game_tree(self.h, slot, max_nodes, _ptr(nodes), _ptr(edges), ctypes.byref(n)))
+        return nodes[:n.value], edges[:n.value]
+
+    def root_policy(self, slot):
+        out = np.zeros(self.P, np.float32)
+        check(lib().coffee_match_root_policy(self.h, slot, _ptr(out)))
+        return out
+
+    def close(self):
+        if self.h:
+            lib().coffee_match_destroy(self.h)
             self.h = ctypes.c_void_p()
 
     def __del__(self):

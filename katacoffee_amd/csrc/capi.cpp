@@ -426,6 +426,145 @@ int coffee_selfplay_destroy(coffee_selfplay* h) {
   });
 }
 
+// ---- two-network match play: the self-play engine in match mode ----
+
+void coffee_match_params_default(coffee_search_params* p) {
+  if(!p)
+    return;
+  coffee_search_params_default(p);  // play settings all off
+  // cpp/configs/training/gatekeeper1.cfg:49, :72-80, :95-106
+  p->max_visits = 150;
+  p->chosen_move_temperature_early = 0.5f;
+  p->chosen_move_temperature_halflife = 19.0f;
+  p->chosen_move_temperature = 0.2f;
+  p->chosen_move_subtract = 0.0f;
+  p->chosen_move_prune = 1.0f;
+  p->use_lcb_for_selection = 1;
+  p->lcb_stdevs = 5.0f;
+  p->min_visit_prop_for_lcb = 0.15f;
+  p->cpuct_exploration = 1.1f;
+  p->cpuct_exploration_log = 0.0f;
+  p->fpu_reduction_max = 0.2f;
+  p->root_fpu_reduction_max = 0.1f;
+  p->value_weight_exponent = 0.5f;
+  p->subtree_value_bias_factor = 0.35f;
+  p->subtree_value_bias_weight_exponent = 0.8f;
+  p->use_graph_search = 1;
+  // not in that config: the reference's defaults (searchparams.cpp), root noise off
+  p->root_noise_enabled = 0;
+  p->root_policy_temperature = 1.0f;
+  p->root_policy_temperature_early = 1.0f;
+  p->root_desired_per_child_visits_coeff = 0.0f;
+  p->root_num_symmetries_to_sample = 1;
+}
+
+struct coffee_match {
+  SelfplayEngine* eng;
+};
+
+int coffee_match_create(const coffee_match_config* cfg, coffee_match** out) {
+  return guarded([&] {
+    need(cfg && out, "NULL argument");
+    coffee_match* h = new coffee_match{nullptr};
+    try {
+      h->eng = new SelfplayEngine(*cfg);  // validates the config before its first HIP call
+    } catch(...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+  });
+}
+
+int coffee_match_step(coffee_match* h, int rounds, void* stream) {
+  return guarded([&] {
+    need(h && h->eng, "NULL handle");
+    need(rounds >= 0, "rounds must be >= 0");
+    h->eng->step(rounds, (hipStream_t)stream);
+  });
+}
+
+int coffee_match_sync(coffee_match* h) {
+  return guarded([&] {
+    need(h && h->eng, "NULL handle");
+    h->eng->sync();
+  });
+}
+
+int coffee_match_stream(coffee_match* h, void** stream) {
+  return guarded([&] {
+    need(h && h->eng && stream, "NULL argument");
+    *stream = (void*)h->eng->stream();
+  });
+}
+
+int coffee_match_destroy(coffee_match* h) {
+  return guarded([&] {
+    if(h) {
+      delete h->eng;
+      delete h;
+    }
+  });
+}
+
+int coffee_match_stats_get(coffee_match* h, coffee_match_stats* out) {
+  return guarded([&] {
+    need(h && h->eng && out, "NULL argument");
+    h->eng->matchStats(*out);
+  });
+}
+
+int coffee_match_drain_games(coffee_match* h, int max_games, int32_t* header, uint8_t* moves, int* n_out) {
+  return guarded([&] {
+    need(h && h->eng && n_out, "NULL argument");
+    need(max_games >= 0, "max_games must be >= 0");
+    *n_out = h->eng->drainGames(max_games, header, moves);
+  });
+}
+
+int coffee_match_score(const int32_t* header, int n, double* candidate_points, double* baseline_points) {
+  return guarded([&] {
+    need(n >= 0 && (n == 0 || header) && candidate_points && baseline_points, "bad argument");
+    double c = 0.0, b = 0.0;
+    for(int i = 0; i < n; i++) {
+      const int winner = header[5 * i + 3], cand = header[5 * i + 4];
+      need((cand == 1 || cand == 2) && winner >= 0 && winner <= 2, "header: winner 0..2 and candidate colour 1 or 2");
+      if(winner == 0) {
+        c += 0.5;
+        b += 0.5;
+      } else if(winner == cand) {
+        c += 1.0;
+      } else {
+        b += 1.0;
+      }
+    }
+    *candidate_points = c;
+    *baseline_points = b;
+  });
+}
+
+int coffee_match_game_info(coffee_match* h, int slot, int64_t* info) {
+  return guarded([&] {
+    need(h && h->eng && info, "NULL argument");
+    h->eng->gameInfo(slot, info);
+  });
+}
+
+int coffee_match_game_tree(coffee_match* h, int slot, int max_nodes, uint32_t* nodes, uint32_t* edges,
+                           int* n_nodes) {
+  return guarded([&] {
+    need(h && h->eng && n_nodes, "NULL argument");
+    *n_nodes = h->eng->gameTree(slot, max_nodes, nodes, edges);
+  });
+}
+
+int coffee_match_root_policy(coffee_match* h, int slot, float* out) {
+  return guarded([&] {
+    need(h && h->eng && out, "NULL argument");
+    h->eng->rootPolicy(slot, out);
+  });
+}
+
 int coffee_write_npz(const char* path, int n, int x, int y, const uint8_t* bin, const float* glob,
                      const int16_t* pol, const float* gtgt, const int8_t* value) {
   return guarded([&] {

@@ -41,31 +41,12 @@
 
 #include "../../include/katacoffee.h"
 #include "cli_config.h"
+#include "cli_util.h"
 
 using namespace kccli;
 
 static std::atomic<bool> gStop(false);
 static void onSignal(int) { gStop = true; }
-
-static std::mutex gLogMu;
-static FILE* gLog = nullptr;
-static void logf(const char* fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  std::lock_guard<std::mutex> lk(gLogMu);
-  time_t t = time(nullptr);
-  char ts[32];
-  strftime(ts, sizeof(ts), "%Y-%m-%d %H:%M:%S", localtime(&t));
-  fprintf(stdout, "%s: %s\n", ts, buf);
-  fflush(stdout);
-  if(gLog) {
-    fprintf(gLog, "%s: %s\n", ts, buf);
-    fflush(gLog);
-  }
-}
 
 static void die(const std::string& msg) {
   fprintf(stderr, "katago selfplay: %s\n", msg.c_str());
@@ -77,39 +58,11 @@ static void check(int rc, const char* what) {
     die(std::string(what) + ": " + coffee_last_error());
 }
 
-// Newest regular file in dir ("" if none); its mtime in *mt.
-static std::string newestModelOrEmpty(const std::string& dir, time_t* mt) {
-  DIR* d = opendir(dir.c_str());
-  if(!d)
-    return "";
-  std::string best;
-  time_t bestT = 0;
-  while(dirent* e = readdir(d)) {
-    if(e->d_name[0] == '.')
-      continue;
-    std::string p = dir + "/" + e->d_name;
-    struct stat st;
-    if(stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (best.empty() || st.st_mtime > bestT)) {
-      best = p;
-      bestT = st.st_mtime;
-    }
-  }
-  closedir(d);
-  if(mt)
-    *mt = bestT;
-  return best;
-}
-
 static std::string newestModel(const std::string& dir) {
   const std::string m = newestModelOrEmpty(dir, nullptr);
   if(m.empty())
     die("no model file in " + dir);
   return m;
-}
-
-static std::string modelNameOf(const std::string& path) {
-  std::string n = path.substr(path.find_last_of('/') + 1);
-  return n.find('.') != std::string::npos ? n.substr(0, n.find('.')) : n;
 }
 
 // The models directory as seen by all GPU threads: version bumps when a newer file
@@ -141,20 +94,6 @@ struct ModelWatch {
   }
 };
 static ModelWatch gModels;
-
-static void mkdirs(const std::string& path) {
-  std::string cur;
-  std::stringstream ss(path);
-  std::string part;
-  if(!path.empty() && path[0] == '/')
-    cur = "/";
-  while(std::getline(ss, part, '/')) {
-    if(part.empty())
-      continue;
-    cur += part + "/";
-    mkdir(cur.c_str(), 0755);
-  }
-}
 
 struct RowSink {
   std::string dir;
@@ -198,9 +137,7 @@ struct RowSink {
   }
 };
 
-// Finished games as SGF, one game per line of <dir>/<hex>.sgfs (sgf.cpp:1526-1700:
-// FF[4] GM[Coffee] SZ WLL PB PW RE, moves B[xyd] / W[xyd] with d = a..d for N, W,
-// NW, NE; Coffee draws — SPEC B16 — are RE[0]).
+// Finished games as SGF, one game per line of <dir>/<hex>.sgfs (cli_util.h sgfGame).
 struct SgfSink {
   std::string dir, modelName;
   int x, y, winLen;
@@ -219,27 +156,8 @@ struct SgfSink {
         die("cannot write sgfs in " + dir);
     }
     const int A = x * y;
-    const char* coord = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ";
     for(int i = 0; i < n; i++) {
-      const int32_t* h = hdr + 4 * i;
-      const char* res = h[3] == 1 ? "B+" : (h[3] == 2 ? "W+" : "0");
-      std::string g = "(;FF[4]GM[Coffee]";
-      g += x == y ? "SZ[" + std::to_string(x) + "]" : "SZ[" + std::to_string(x) + ":" + std::to_string(y) + "]";
-      g += "WLL[" + std::to_string(winLen) + "]PB[" + modelName + "]PW[" + modelName + "]RE[" + res + "]";
-      g += "C[startTurnIdx=0,initTurnNum=0,gameId=" + std::to_string(h[0]) + ":" + std::to_string(h[1]) +
-           ",gtype=normal]";
-      for(int t = 0; t < h[2] && t < A; t++) {
-        const int cell = mv[((size_t)i * A + t) * 2], d = mv[((size_t)i * A + t) * 2 + 1];
-        g += t % 2 == 0 ? ";B[" : ";W[";
-        g += coord[cell % x];
-        g += coord[cell / x];
-        g += (char)('a' + d);
-        g += "]";
-        if(t + 1 == h[2])
-          g += std::string("C[result=") + res + "]";
-      }
-      g += ")\n";
-      fputs(g.c_str(), f);
+      fputs(sgfGame(x, y, winLen, modelName, modelName, hdr + 4 * i, mv + (size_t)i * A * 2).c_str(), f);
       games++;
     }
     fflush(f);
@@ -375,7 +293,16 @@ static void runGpu(int gpu, int server, int perGpu, int slot, int share, const S
        (long long)(rowsBefore + sink.rowsWritten), (long long)games.games);
 }
 
+#ifdef KATAGO_GATEKEEPER
+int gatekeeperMain(int argc, char** argv);  // cli_gatekeeper.cpp
+#endif
+
 int main(int argc, char** argv) {
+#ifdef KATAGO_GATEKEEPER
+  // (a build of this file alone -- the sanitizer harness -- has the selfplay command only)
+  if(argc >= 2 && std::string(argv[1]) == "gatekeeper")
+    return gatekeeperMain(argc, argv);
+#endif
   if(argc < 2 || std::string(argv[1]) != "selfplay")
     die("usage: katago selfplay -config <cfg> -models-dir <dir> -output-dir <dir> [-max-games-total N] "
         "[-override-config k=v,...]");

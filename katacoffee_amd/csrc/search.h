@@ -154,6 +154,7 @@ struct Edge {
 // A finished game's move record (SGF output): header then the moves in order.
 struct GameRec {
   int32_t slot, gameNum, numMoves, winner;  // winner 0 draw, 1 black, 2 white
+  int32_t candidate;                        // match mode: the candidate's colour (1 black, 2 white), else 0
   uint8_t cell[MAX_AREA], dir[MAX_AREA];
 };
 
@@ -328,13 +329,34 @@ struct SearchDev {
   DPtr<GameRec> gRec;               // [gCap]
   DPtr<unsigned long long> gCount;
   DPtr<unsigned long long> gDropped;
+  // two-network match play (the MATCH kernel instantiations; DESIGN.md "Match play"): net 0
+  // uses the arrays above, net 1 these.  matchNet() names the net of a game's evaluations.
+  int32_t matchMode;
+  DPtr<int32_t> nnIdx1;       // [G] net 1's compacted rows
+  DPtr<int32_t> nnCount1;     // rows in nnIdx1
+  DPtr<int32_t> nnPeak;       // [2] largest batch of each net so far (stats)
+  DPtr<unsigned long long> nnNetEvals;  // [2] rows listed for each net so far (stats)
+  DPtr<uint64_t> cKey1;
+  DPtr<float> cPol1;
+  DPtr<float> cVal1;
+  DPtr<uint32_t> cTag1;
 };
+
+// Match play: the candidate (net 1) plays black (player 1) in game number n of global
+// slot s iff s + n is even (the reference's {{0,1},{1,0}} pairing, gatekeeper.cpp:111).
+KC_HD int matchCandidateColour(int globalSlot, int gameNum) { return ((globalSlot + gameNum) & 1) == 0 ? 1 : 2; }
+// The net that evaluates everything a game asks for in a round: the one of the ROOT
+// player to move (0 baseline, 1 candidate), whatever the leaf's own player.
+KC_HD int matchNet(int globalSlot, int gameNum, int rootPla) {
+  return rootPla == matchCandidateColour(globalSlot, gameNum) ? 1 : 0;
+}
 
 // Kernel launchers (search.hip).
 void launchSelfplayInit(const SearchDev& d, const SearchDev* dd, hipStream_t st);
 // e0/e1 (optional): events recorded at the kernel's start and end (hipExtLaunchKernel),
 // so the bench times the kernel itself, not the stream gaps around it
 // resetCommit: zero the commit count first (the previous commit consumed its list)
+// (d.matchMode: the launchers below pick the MATCH instantiations; launchCommit then runs no kRows)
 void launchSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEvent_t e0 = nullptr,
                   hipEvent_t e1 = nullptr, bool resetCommit = false);
 // accumulate: add the batch size to *d.nnTimedEvals (rounds whose network launch is timed)

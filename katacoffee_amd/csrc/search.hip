@@ -1168,21 +1168,48 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
 // the slot's tag is loaded too -- a bid of this round (tag != 0) means this round's
 // backups, running beside this selection, write the slot, so the lookup is left to
 // kResolve (LEAF_PENDING); any other slot is not written during the kernel.
-template <int NI>
+//
+// Match play (the MATCH instantiations; DESIGN.md "Match play"): each of the two nets has
+// its own cache, as the reference has one per NNEvaluator.  netOf is the one place the net
+// of a game's evaluations -- and with it the cache -- is derived: the compaction, the
+// lookup and the cache write all go through it.  The root and the game number it reads
+// change only in kCommit (and in a policy-initialisation backup, after its evaluation is
+// consumed), so a round's select, compaction and backup agree, also for a deferred row.
+KC_D int netOf(const SearchDev& d, int g, const GameDev& s) {
+  return matchNet(d.slotBase + g, s.gameNum, s.root.pla);
+}
+struct NNCache {
+  uint64_t* key;
+  float* pol;
+  float* val;
+  uint32_t* tag;
+};
+// The cache of net `net`; without MATCH the single one, whatever `net`.
+template <bool MATCH>
+KC_D NNCache cacheOf(const SearchDev& d, int net) {
+  if constexpr(MATCH) {
+    if(net != 0)
+      return NNCache{d.cKey1, d.cPol1, d.cVal1, d.cTag1};
+  }
+  return NNCache{d.cKey, d.cPol, d.cVal, d.cTag};
+}
+
+template <int NI, bool MATCH = false>
 KC_D void cacheLookup(const GV& v, GameDev& s, bool fused) {
   const SearchDev& d = v.d;
+  const NNCache c = cacheOf<MATCH>(d, MATCH ? netOf(d, v.g, s) : 0);
   const uint64_t k0 = v.nodeKey(s.leafNode)[0], k1 = v.nodeKey(s.leafNode)[1];
   const uint32_t slot = cacheSlot(k0, k1, d.cacheMask);
   const int P = d.P;
-  const float* cp = d.cPol + (size_t)slot * P;
+  const float* cp = c.pol + (size_t)slot * P;
   float pv[NI];
 #pragma unroll
   for(int j = 0; j < NI; j++) {
     const int pos = v.lane + 64 * j;
     pv[j] = pos < P ? cp[pos] : 0.0f;
   }
-  const float cw = d.cVal[2 * (size_t)slot], cl = d.cVal[2 * (size_t)slot + 1];
-  const uint32_t tag = fused ? d.cTag[slot] : 0u;
+  const float cw = c.val[2 * (size_t)slot], cl = c.val[2 * (size_t)slot + 1];
+  const uint32_t tag = fused ? c.tag[slot] : 0u;
   s.cSlot = (int32_t)slot;
   if(tag != 0u) {
     s.leafKind = LEAF_PENDING;
@@ -1190,7 +1217,7 @@ KC_D void cacheLookup(const GV& v, GameDev& s, bool fused) {
       d.pendList[atomicAdd(d.pendCount, 1)] = v.g;  // rare: a same-round transposition
     return;
   }
-  if(d.cKey[2 * (size_t)slot] == k0 && d.cKey[2 * (size_t)slot + 1] == k1) {
+  if(c.key[2 * (size_t)slot] == k0 && c.key[2 * (size_t)slot + 1] == k1) {
     s.leafKind = LEAF_CACHED;
     s.cHitWin = cw;
     s.cHitLoss = cl;
@@ -1234,7 +1261,7 @@ KC_D void finishSelect(const GV& v, GameDev& s, DRng& rng) {
 
 // One game's selection.  s: the game's LDS copy, already holding its state when `loaded`
 // (the fused kernel's backup just ran; every path below then stores it).  rootPol: LDS [MAX_P].
-template <int NI>
+template <int NI, bool MATCH = false>
 KC_D void selectBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bool loaded, bool fused,
                      uint32_t* hasBits, float* rootPol) {
   GV v(d, T, g);
@@ -1310,7 +1337,7 @@ KC_D void selectBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   } else {
     descend<NI>(v, s, hasBits, rootPol);
     if(s.leafKind == LEAF_NN && d.cacheOn)
-      cacheLookup<NI>(v, s, fused);
+      cacheLookup<NI, MATCH>(v, s, fused);
   }
   const unsigned long long t2 = SPROF_NOW();
   (void)t2;
@@ -1326,7 +1353,7 @@ KC_D void selectBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   SPROF_FLUSH();
 }
 
-template <int NI>
+template <int NI, bool MATCH = false>
 __global__ void __launch_bounds__(64, NI <= 2 ? 4 : 2) kSelect(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp,
                                                                 int resetCommit) {
   const SearchDev& d = *dp;
@@ -1340,7 +1367,7 @@ __global__ void __launch_bounds__(64, NI <= 2 ? 4 : 2) kSelect(const SearchDev* 
   __shared__ uint32_t hasBits[(MAX_P + 31) / 32];
   __shared__ GameDev s;
   __shared__ float rootPol[MAX_P];
-  selectBody<NI>(d, *Tp, g, s, false, false, hasBits, rootPol);
+  selectBody<NI, MATCH>(d, *Tp, g, s, false, false, hasBits, rootPol);
 }
 
 // The selections a fused kernel left pending: the cache slot is final now (every backup
@@ -1568,6 +1595,7 @@ KC_D void firstExpansion(const GV& v, int ni, const float (&pv)[NI]) {
 
 // kBackup: NN post-processing + leaf value + path backup.
 KC_D bool setMoveLimits(const GV& v, GameDev& s, DRng& rng, float lastWL);
+template <bool MATCH = false>
 KC_D void finishGameRecord(const GV& v, const GameDev& s, DRng& rng, float* scratch);
 KC_D void startGame(const GV& v, GameDev& s);
 template <int NI>
@@ -1660,7 +1688,7 @@ KC_D bool initMove(const GV& v, GameDev& s, const float* o, float* scratch /* LD
 // stored -- selectBody stores it on every path).
 // fused (kBackupSelect): a cache-slot winner leaves the slot's tag set -- the selections
 // running beside it treat the slot as being written -- and kResolve clears it.
-template <int NI>
+template <int NI, bool MATCH = false>
 KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bool fused, float* scratch) {
   if(d.nnDefer[g])  // a deferred leaf is backed up in a later round
     return false;
@@ -1766,22 +1794,23 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
           // game + 1 over the round's batch); the highest bidder stores its payload
           // and clears the tag, deterministic whatever the block order.  Nothing
           // reads the table in this kernel (hits were copied by kSelect).
+          const NNCache c = cacheOf<MATCH>(d, MATCH ? netOf(d, g, s) : 0);
           const uint32_t slot = (uint32_t)s.cSlot;
-          if(d.cTag[slot] == (uint32_t)g + 1u) {
-            float* cp = d.cPol + (size_t)slot * P;
+          if(c.tag[slot] == (uint32_t)g + 1u) {
+            float* cp = c.pol + (size_t)slot * P;
 #pragma unroll
             for(int j = 0; j < NI; j++)
               if(v.lane + 64 * j < P)
                 cp[v.lane + 64 * j] = pv[j];
             if(v.lane == 0) {
-              d.cVal[2 * (size_t)slot] = w;
-              d.cVal[2 * (size_t)slot + 1] = l;
-              d.cKey[2 * (size_t)slot] = v.nodeKey(s.leafNode)[0];
-              d.cKey[2 * (size_t)slot + 1] = v.nodeKey(s.leafNode)[1];
+              c.val[2 * (size_t)slot] = w;
+              c.val[2 * (size_t)slot + 1] = l;
+              c.key[2 * (size_t)slot] = v.nodeKey(s.leafNode)[0];
+              c.key[2 * (size_t)slot + 1] = v.nodeKey(s.leafNode)[1];
               if(fused)
                 d.cClear[g] = slot + 1u;
               else
-                d.cTag[slot] = 0;
+                c.tag[slot] = 0;
             }
           }
         }
@@ -1836,7 +1865,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   return true;
 }
 
-template <int NI>
+template <int NI, bool MATCH = false>
 __global__ void __launch_bounds__(64, NI <= 4 ? 4 : 3) kBackup(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp) {
   const SearchDev& d = *dp;
   const int g = blockIdx.x;
@@ -1844,7 +1873,7 @@ __global__ void __launch_bounds__(64, NI <= 4 ? 4 : 3) kBackup(const SearchDev* 
     return;
   __shared__ __attribute__((aligned(16))) float scratch[3 * MAX_P];
   __shared__ GameDev s;
-  backupBody<NI>(d, *Tp, g, s, false, scratch);
+  backupBody<NI, MATCH>(d, *Tp, g, s, false, scratch);
 }
 
 // Round r's backup and round r+1's selection of one game in one kernel (no commit between
@@ -3147,6 +3176,10 @@ KC_D int resolveTurnWeights(const GV& v, const GameDev& s, DRng& rng, float* vs 
   return total;
 }
 
+// MATCH: the record also carries the candidate's colour, and no rows are reserved (match
+// play writes none: kRows does not run and nothing counts as dropped).  The turn weights
+// are still resolved, so the game stream advances as in self-play.
+template <bool MATCH>
 KC_D void finishGameRecord(const GV& v, const GameDev& s, DRng& rng, float* scratch) {
   const SearchDev& d = v.d;
   const int numMoves = s.numTurns;
@@ -3170,6 +3203,7 @@ KC_D void finishGameRecord(const GV& v, const GameDev& s, DRng& rng, float* scra
         gr->gameNum = (int32_t)s.gameNum;
         gr->numMoves = numMoves;
         gr->winner = s.root.winner;
+        gr->candidate = MATCH ? matchCandidateColour(d.slotBase + v.g, (int)s.gameNum) : 0;
       }
       for(int t = v.lane; t < numMoves; t += 64) {
         gr->cell[t] = (uint8_t)tr[t].cell;
@@ -3177,6 +3211,8 @@ KC_D void finishGameRecord(const GV& v, const GameDev& s, DRng& rng, float* scra
       }
     }
   }
+  if constexpr(MATCH)
+    return;
   if(v.lane == 0) {
     unsigned long long base = atomicAdd(d.rCount, (unsigned long long)numRows);
     bool fits = true;
@@ -3386,7 +3422,9 @@ __global__ void __launch_bounds__(64 * ROWS_WAVES) kRows(const SearchDev* __rest
 
 // oracle commitMove (getChosenMoveLoc searchresults.cpp:435-453, extract*Targets
 // play.cpp:635-704, getPolicySurpriseAndEntropy searchresults.cpp:486-550, makeMove)
-template <int NI>
+// MATCH (two-network match play): the game record carries the candidate's colour and no
+// rows are emitted; the config admits no side positions, forks or tree positions there.
+template <int NI, bool MATCH = false>
 __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp) {
   const SearchDev& d = *dp;
   if((int)blockIdx.x >= *d.commitCount)
@@ -3411,7 +3449,7 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
   if(s.root.finished) {
     // a policy-initialisation move ended the game: nothing was searched, no rows
     // (the reference's main loop does not run, play.cpp:1262-1264)
-    finishGameRecord(v, s, rng, reinterpret_cast<float*>(lds) + 2 * MAX_P);
+    finishGameRecord<MATCH>(v, s, rng, reinterpret_cast<float*>(lds) + 2 * MAX_P);
     s.gamesFinished++;
     s.gameNum++;
     s.sideNext = 0;
@@ -3508,7 +3546,7 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
   waveSync();
   if(s.root.finished) {
     [[maybe_unused]] const unsigned long long t3 = SPROF_NOW();
-    finishGameRecord(v, s, rng, tmp);
+    finishGameRecord<MATCH>(v, s, rng, tmp);
     [[maybe_unused]] const unsigned long long t4 = SPROF_NOW();
     s.gamesFinished++;
     s.gameNum++;
@@ -3566,10 +3604,132 @@ constexpr int CP_RESOLVE_WAVES = 4;
 // (The resolving instance alone holds the LDS game copies: the plain one, which the separate
 // round kernels and the default precision's network run beside, keeps its 132 bytes of LDS
 // and fits on a CU next to any network workgroup.)
-template <int NI, bool RESOLVE>
+//
+// Match play (MATCH; never after a fused round): the same pass with four running counts,
+// net x (at or past the pointer / before it), as four 16-bit fields of a 64-bit word
+// (bits 48.. net 1 past, 32.. net 0 past, 16.. net 1 before, 0.. net 0 before) and the
+// same ballot walk.  The cap rule is the single-net one on both nets' rows together: a
+// row's joint position (both nets' fields added) decides whether it is taken, deferred
+// and where the pointer moves; a taken row goes to its own net's list (nnIdx / nnIdx1) at
+// its position among that net's rows, so each list keeps the joint order, and bids in its
+// net's cache.  The net comes from netOf on the game's stored state, read for needing
+// games only.  Same 256-thread launch; the 64-bit partial sums take 272 bytes of LDS
+// instead of 144 and no game copy, so the workgroup still fits beside any network one.
+template <int NI>
+KC_D void compactMatch(const SearchDev& d, int accumulate) {
+  __shared__ uint64_t wsum[16], wpre[17];
+  const int nt = blockDim.x, nw = nt >> 6;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int nch = (d.G + 63) >> 6;
+  const int cpw = (nch + nw - 1) / nw;  // <= 64 chunks per wave, as in the single-net pass
+  const int g0 = w * cpw * 64 + lane;
+  const int p = *d.nnRR;
+  // the two nets' lists and cache tags as plain (wave-uniform) pointers: a lane picks by its game's net
+  int32_t* const idxOf[2] = {d.nnIdx, d.nnIdx1};
+  uint32_t* const tagOf[2] = {cacheOf<true>(d, 0).tag, cacheOf<true>(d, 1).tag};
+  uint64_t need = 0, net1 = 0;  // bit k: game g0 + 64 k needs the network / is evaluated by net 1
+  for(int k = 0; k < cpw; k++) {
+    const int i = g0 + 64 * k;
+    if(i < d.G && d.nnNeed[i]) {
+      need |= 1ull << k;
+      net1 |= (uint64_t)netOf(d, i, d.games[i]) << k;
+    }
+  }
+  const uint64_t atOrPast = p <= g0 ? ~0ull : (p - g0 > 64 * 63 ? 0ull : ~0ull << ((p - g0 + 63) / 64));
+  uint64_t c = ((uint64_t)__popcll(need & atOrPast & net1) << 48) + ((uint64_t)__popcll(need & atOrPast & ~net1) << 32) +
+               ((uint64_t)__popcll(need & ~atOrPast & net1) << 16) + (uint64_t)__popcll(need & ~atOrPast & ~net1);
+#pragma unroll
+  for(int off = 32; off >= 1; off >>= 1)
+    c += (uint64_t)__shfl_xor((long long)c, off, 64);
+  if(lane == 0)
+    wsum[w] = c;
+  __syncthreads();
+  if(t < 64) {
+    uint64_t x = t < nw ? wsum[t] : 0ull, xi = x;
+#pragma unroll
+    for(int off = 1; off < 16; off <<= 1) {
+      const uint64_t v = (uint64_t)__shfl_up((long long)xi, off, 64);
+      if(t >= off)
+        xi += v;
+    }
+    if(t < 16)
+      wpre[t] = xi - x;
+    if(t == 15)
+      wpre[16] = xi;
+  }
+  __syncthreads();
+  const uint64_t all = wpre[16], excl = wpre[w];
+  auto field = [](uint64_t x, int f) { return (int)((x >> (16 * f)) & 0xFFFFull); };
+  // per net n: rows at or past the pointer in all, and this wave's running positions
+  const int hiAll[2] = {field(all, 2), field(all, 3)};
+  const int totalHi = hiAll[0] + hiAll[1];
+  const int total = totalHi + field(all, 0) + field(all, 1), cap = d.nnCap;
+  int oh[2] = {field(excl, 2), field(excl, 3)};
+  int ol[2] = {hiAll[0] + field(excl, 0), hiAll[1] + field(excl, 1)};
+  const int taken = min(total, cap);
+  const uint64_t below = (1ull << lane) - 1ull;
+  for(int k = 0; k < cpw; k++) {
+    const int i = g0 + 64 * k;
+    const bool nd = (need >> k) & 1u;
+    const int n = (int)((net1 >> k) & 1u);
+    const bool past = i >= p;
+    const uint64_t b1 = ballot(nd && n == 1), b0 = ballot(nd && n == 0);
+    const uint64_t g1 = ballot(nd && n == 1 && past), g0b = ballot(nd && n == 0 && past);
+    if(nd) {
+      // position among the net's own rows and among both nets' rows, in cyclic game order
+      const int own = past ? oh[n] + __popcll((n ? g1 : g0b) & below)
+                           : ol[n] + __popcll((n ? b1 & ~g1 : b0 & ~g0b) & below);
+      const int other = past ? oh[1 - n] + __popcll((n ? g0b : g1) & below)
+                             : ol[1 - n] + __popcll((n ? b0 & ~g0b : b1 & ~g1) & below);
+      const int pos = own + other;
+      const bool in = pos < cap;
+      if(in) {
+        (n ? idxOf[1] : idxOf[0])[own] = i;  // own <= pos < cap <= G
+        const uint32_t bid = d.nnBid[i];
+        if(bid != ~0u)
+          atomicMax(&(n ? tagOf[1] : tagOf[0])[bid], (uint32_t)i + 1u);
+      }
+      d.nnDefer[i] = in ? 0 : 1;
+      if(total > cap && pos == cap - 1)
+        *d.nnRR = i + 1 < d.G ? i + 1 : 0;
+      if(pos == taken - 1) {
+        // the last row taken: its net's list ends with it, the other list holds the rest
+        const int cn[2] = {n ? taken - own - 1 : own + 1, n ? own + 1 : taken - own - 1};
+        *d.nnCount = cn[0];
+        *d.nnCount1 = cn[1];
+        d.nnPeak[0] = max(d.nnPeak[0], cn[0]);
+        d.nnPeak[1] = max(d.nnPeak[1], cn[1]);
+        d.nnNetEvals[0] += (unsigned long long)cn[0];
+        d.nnNetEvals[1] += (unsigned long long)cn[1];
+      }
+    } else if(i < d.G) {
+      d.nnDefer[i] = 0;
+    }
+    oh[0] += __popcll(g0b);
+    oh[1] += __popcll(g1);
+    ol[0] += __popcll(b0 & ~g0b);
+    ol[1] += __popcll(b1 & ~g1);
+  }
+  if(t == nt - 1) {
+    if(total == 0) {
+      *d.nnCount = 0;
+      *d.nnCount1 = 0;
+    }
+    *d.pendCount = 0;
+    if(accumulate)
+      *d.nnTimedEvals += (unsigned long long)taken;
+  }
+}
+
+template <int NI, bool RESOLVE, bool MATCH = false>
 __global__ void __launch_bounds__(1024) kCompact(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp,
                                                  int accumulate) {
   const SearchDev& d = *dp;
+  if constexpr(MATCH) {
+    static_assert(!RESOLVE, "match play runs no fused rounds");
+    compactMatch<NI>(d, accumulate);
+    return;
+  }
   __shared__ uint32_t wsum[16], wpre[17];
   const int nt = blockDim.x, nw = nt >> 6;  // 256 or 1024 threads (launchCompact)
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -3837,7 +3997,9 @@ void launchCompact(const SearchDev& d, const SearchDev* dd, hipStream_t st, bool
   const int nt = d.G <= 4 * 64 * CP_CH ? 256 : 1024;  // 1024 only past 8192 games per engine
   const DTables* T = d.T;
   const int a = accumulate ? 1 : 0;
-  if(!resolve)
+  if(d.matchMode)
+    hipLaunchKernelGGL((kCompact<2, false, true>), dim3(1), dim3(nt), 0, st, dd, T, a);
+  else if(!resolve)
     hipLaunchKernelGGL((kCompact<2, false>), dim3(1), dim3(nt), 0, st, dd, T, a);
   else
     switch(laneItems(d.P)) {
@@ -3862,6 +4024,15 @@ void launchSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEv
                   bool resetCommit) {
   const DTables* T = d.T;
   const int rc = resetCommit ? 1 : 0;
+  if(d.matchMode) {
+    switch(laneItems(d.P)) {
+      case 2: launchEv(kSelect<2, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
+      case 4: launchEv(kSelect<4, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
+      default: launchEv(kSelect<7, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
+    }
+    KC_HIP(hipGetLastError());
+    return;
+  }
   switch(laneItems(d.P)) {
     case 2: launchEv(kSelect<2>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
     case 4: launchEv(kSelect<4>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
@@ -3872,6 +4043,15 @@ void launchSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEv
 
 void launchBackup(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   const DTables* T = d.T;
+  if(d.matchMode) {
+    switch(laneItems(d.P)) {
+      case 2: launchEv(kBackup<2, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
+      case 4: launchEv(kBackup<4, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
+      default: launchEv(kBackup<7, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
+    }
+    KC_HIP(hipGetLastError());
+    return;
+  }
   switch(laneItems(d.P)) {
     case 2: launchEv(kBackup<2>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
     case 4: launchEv(kBackup<4>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
@@ -3902,6 +4082,15 @@ void launchResolve(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
 
 void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
   const size_t lds = commitLdsBytes(d.cap);
+  if(d.matchMode) {  // no kRows: match play writes no training rows
+    switch(laneItems(d.P)) {
+      case 2: hipLaunchKernelGGL((kCommit<2, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+      case 4: hipLaunchKernelGGL((kCommit<4, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+      default: hipLaunchKernelGGL((kCommit<7, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+    }
+    KC_HIP(hipGetLastError());
+    return;
+  }
   switch(laneItems(d.P)) {
     case 2: hipLaunchKernelGGL(kCommit<2>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;
     case 4: hipLaunchKernelGGL(kCommit<4>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;

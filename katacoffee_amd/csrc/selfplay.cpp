@@ -98,7 +98,57 @@ static T* devAlloc(std::vector<void*>& owned, size_t count, bool zero = true) {
   return reinterpret_cast<T*>(p);
 }
 
-SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c) {
+// The settings match play rejects (DESIGN.md "Match play"): each side searches with its own
+// net from a cleared tree, and no training rows are made.
+void validateMatchConfig(const coffee_match_config& c) {
+  if(c.x < 2 || c.y < 2 || c.x > MAX_LEN || c.y > MAX_LEN)
+    throw std::invalid_argument("board size must be 2..10 x 2..10");
+  if(c.win_len < 2 || c.win_len > std::max(c.x, c.y))
+    throw std::invalid_argument("win_len must be in 2..max(x, y)");
+  const coffee_search_params& sp = c.search;
+  auto reject = [](bool bad, const char* name, const char* why) {
+    if(bad)
+      throw std::invalid_argument(std::string("match play: ") + name + " " + why);
+  };
+  const char* keeps = "must be off (a kept tree would hold the other net's evaluations)";
+  const char* rows = "must be off (it exists only to make training rows)";
+  reject(sp.cheap_search_prob > 0.0f, "cheap_search_prob", keeps);
+  reject(sp.reduce_visits != 0, "reduce_visits", rows);
+  reject(sp.early_fork_game_prob > 0.0f, "early_fork_game_prob", rows);
+  reject(sp.fork_game_prob > 0.0f, "fork_game_prob", rows);
+  reject(sp.side_position_prob > 0.0f, "side_position_prob", rows);
+  reject(sp.record_tree_positions != 0, "record_tree_positions", rows);
+  reject(sp.policy_surprise_data_weight != 0.0f, "policy_surprise_data_weight", rows);
+  reject(sp.value_surprise_data_weight != 0.0f, "value_surprise_data_weight", rows);
+}
+
+// The self-play config a match engine is built on: one row of row buffer (never written).
+coffee_selfplay_config SelfplayEngine::matchBase(const coffee_match_config& c) {
+  validateMatchConfig(c);  // before the first HIP call
+  coffee_selfplay_config b;
+  memset(&b, 0, sizeof(b));
+  b.x = c.x;
+  b.y = c.y;
+  b.win_len = c.win_len;
+  b.num_games = c.num_games;
+  b.node_cap = c.node_cap;
+  b.row_capacity = 1;
+  b.seed = c.seed;
+  b.slot_base = c.slot_base;
+  b.use_fake_net = 1;  // the two nets come from matchPaths
+  b.commit_interval = c.commit_interval;
+  b.search = c.search;
+  b.nn_cache_log2 = c.nn_cache_log2;
+  b.nn_batch_cap = c.nn_batch_cap;
+  b.nn_precision = c.nn_precision;
+  b.start_stagger = c.start_stagger;
+  b.engines_per_device = c.engines_per_device;
+  return b;
+}
+
+SelfplayEngine::SelfplayEngine(const coffee_match_config& c) : SelfplayEngine(matchBase(c), c.model_path) {}
+
+SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* const* matchPaths) {
   if(c.num_games <= 0)
     throw std::invalid_argument("num_games must be positive");
   if(c.num_games > 65535)  // kCompact packs two per-device game counts into 16-bit halves
@@ -146,11 +196,18 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c) {
   const int G = c.num_games, P = ht.P, A = ht.A;
   const int ttCap = nextPow2(2 * cap);
   const int rowCap = c.row_capacity > 0 ? c.row_capacity : 4 * G * A;
-  if(!c.use_fake_net) {
+  if(matchPaths) {
+    numNets_ = 2;
+    for(int n = 0; n < 2; n++)
+      if(matchPaths[n]) {
+        nets_[n].model.reset(new ModelHost(loadModel(matchPaths[n])));
+        nets_[n].nn.reset(new NNEngine(*nets_[n].model, c.x, c.y, c.win_len, c.nn_precision));
+      }
+  } else if(!c.use_fake_net) {
     if(!c.model_path)
       throw std::invalid_argument("model_path required unless use_fake_net");
-    model_.reset(new ModelHost(loadModel(c.model_path)));
-    nn_.reset(new NNEngine(*model_, c.x, c.y, c.win_len, c.nn_precision));
+    nets_[0].model.reset(new ModelHost(loadModel(c.model_path)));
+    nets_[0].nn.reset(new NNEngine(*nets_[0].model, c.x, c.y, c.win_len, c.nn_precision));
   }
   nnPath_ = c.nn_precision;
   xLen_ = c.x;
@@ -245,6 +302,19 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c) {
     d.cPol = devAlloc<float>(owned_, entries * P, false);
     d.cVal = devAlloc<float>(owned_, entries * 2, false);
     d.cTag = devAlloc<uint32_t>(owned_, entries);
+    if(matchPaths) {  // net 1's own cache
+      d.cKey1 = devAlloc<uint64_t>(owned_, entries * 2);
+      d.cPol1 = devAlloc<float>(owned_, entries * P, false);
+      d.cVal1 = devAlloc<float>(owned_, entries * 2, false);
+      d.cTag1 = devAlloc<uint32_t>(owned_, entries);
+    }
+  }
+  if(matchPaths) {
+    d.matchMode = 1;
+    d.nnIdx1 = devAlloc<int32_t>(owned_, G);
+    d.nnCount1 = devAlloc<int32_t>(owned_, 1);
+    d.nnPeak = devAlloc<int32_t>(owned_, 2);
+    d.nnNetEvals = devAlloc<unsigned long long>(owned_, 2);
   }
   d.cClear = devAlloc<uint32_t>(owned_, G);
   d.pendList = devAlloc<int32_t>(owned_, G, false);
@@ -263,8 +333,10 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c) {
     if(t)
       auditTol_ = (float)atof(t);
   }
-  auditOut_ = devAlloc<float>(owned_, (size_t)G * (P + 4), false);
-  auditMax_ = devAlloc<unsigned>(owned_, 1);
+  for(int n = 0; n < numNets_; n++) {
+    nets_[n].auditOut = devAlloc<float>(owned_, (size_t)G * (P + 4), false);
+    nets_[n].auditMax = devAlloc<unsigned>(owned_, 1);
+  }
   d.gCap = 2 * G;
   d.gRec = devAlloc<GameRec>(owned_, (size_t)d.gCap, false);
   d.gCount = devAlloc<unsigned long long>(owned_, 1);
@@ -288,7 +360,8 @@ SelfplayEngine::~SelfplayEngine() {
   }
   for(hipEvent_t e : evPool_)
     (void)hipEventDestroy(e);
-  nn_.reset();
+  for(Net& n : nets_)
+    n.nn.reset();
   for(void* p : owned_)
     (void)hipFree(p);
   if(stream_)
@@ -344,9 +417,12 @@ void SelfplayEngine::resolveTiming() {
 }
 
 bool SelfplayEngine::fuseNow() const {
+  if(hd_.matchMode)  // match play always runs the separate select and backup kernels
+    return false;
   if(fuseRounds_ >= 0)
     return fuseRounds_ == 1;
-  return !nn_ || (nn_->fused() && nn_->precision() == NN_FAST);
+  const std::unique_ptr<NNEngine>& nn = nets_[0].nn;
+  return !nn || (nn->fused() && nn->precision() == NN_FAST);
 }
 
 void SelfplayEngine::step(int rounds, hipStream_t st) {
@@ -368,23 +444,10 @@ void SelfplayEngine::step(int rounds, hipStream_t st) {
     }
     commitReset_ = false;
     launchCompact(d, dd_, st, t1, selected && resolveInCompact_);
-    timedKernel(1, t1, [&](hipEvent_t a, hipEvent_t b) {
-      const int rows = std::min(d.G, d.nnCap);  // grid bound; the batch is *d.nnCount rows
-      if(nn_) {
-        nn_->forward(rows, d.nnIn, d.nnOut, st, d.nnCount, d.nnIdx, a, b);
-      } else {
-        if(a)
-          KC_HIP(hipEventRecord(a, st));
-        launchFakeNet(T_, rows, d.nnIn, d.nnOut, st, d.nnCount, d.nnIdx);
-        if(b)
-          KC_HIP(hipEventRecord(b, st));
-      }
-    });
-    if(nn_ && nnPath_ == NN_DEFAULT && auditEvery_ > 0 && nn_->precision() == NN_CORRECTED &&
-       nnLaunches_++ % (uint64_t)auditEvery_ == 0) {
-      nn_->audit(std::min(d.G, d.nnCap), d.nnIn, d.nnOut, auditOut_, auditMax_, st, d.nnCount, d.nnIdx);
-      audits_++;
-    }
+    timedKernel(1, t1, [&](hipEvent_t a, hipEvent_t b) { forwardNet(0, d.nnCount, d.nnIdx, st, a, b); });
+    // match play: net 1's list in its own launch, after net 0's on the same stream
+    if(d.matchMode)
+      forwardNet(1, d.nnCount1, d.nnIdx1, st, nullptr, nullptr);
     const bool commitNow = (rounds_ + 1) % (uint64_t)commitInterval_ == 0 || r == rounds - 1;
     if(fuse && !commitNow) {
       const bool t4 = sampleNow(4);
@@ -404,6 +467,27 @@ void SelfplayEngine::step(int rounds, hipStream_t st) {
   }
 }
 
+void SelfplayEngine::forwardNet(int n, const int32_t* count, const int32_t* idx, hipStream_t st, hipEvent_t a,
+                                hipEvent_t b) {
+  const SearchDev& d = hd_;
+  Net& net = nets_[n];
+  const int rows = std::min(d.G, d.nnCap);  // grid bound; the batch is *count rows
+  if(net.nn) {
+    net.nn->forward(rows, d.nnIn, d.nnOut, st, count, idx, a, b);
+  } else {
+    if(a)
+      KC_HIP(hipEventRecord(a, st));
+    launchFakeNet(T_, rows, d.nnIn, d.nnOut, st, count, idx);
+    if(b)
+      KC_HIP(hipEventRecord(b, st));
+  }
+  if(net.nn && nnPath_ == NN_DEFAULT && auditEvery_ > 0 && net.nn->precision() == NN_CORRECTED &&
+     net.nnLaunches++ % (uint64_t)auditEvery_ == 0) {
+    net.nn->audit(rows, d.nnIn, d.nnOut, net.auditOut, net.auditMax, st, count, idx);
+    net.audits++;
+  }
+}
+
 void SelfplayEngine::sync() {
   KC_HIP(hipStreamSynchronize(stream_));
   resolveTiming();
@@ -411,26 +495,30 @@ void SelfplayEngine::sync() {
 }
 
 void SelfplayEngine::auditCheck() {
-  if(!nn_ || audits_ == 0)
-    return;
-  unsigned bits = 0;
-  KC_HIP(hipMemcpy(&bits, auditMax_, 4, hipMemcpyDeviceToHost));
-  float m;
-  memcpy(&m, &bits, 4);
-  auditSeen_ = std::max(auditSeen_, m);
-  if(!(auditSeen_ <= auditTol_) && nn_->precision() == NN_CORRECTED && nnPath_ == NN_DEFAULT) {
-    // the corrected instance missed the default precision's bound on self-play positions:
-    // the same model on the accurate instance from here on (cached evaluations cleared)
-    nn_.reset(new NNEngine(*model_, xLen_, yLen_, winLen_, NN_ACCURATE));
-    auditSwitches_++;
-    const int cap = nnCapFor(hd_.G);
-    if(cap != hd_.nnCap) {
-      hd_.nnCap = cap;
-      KC_HIP(hipMemcpy(&dd_->nnCap, &cap, sizeof(int), hipMemcpyHostToDevice));
+  for(int n = 0; n < numNets_; n++) {
+    Net& net = nets_[n];
+    if(!net.nn || net.audits == 0)
+      continue;
+    unsigned bits = 0;
+    KC_HIP(hipMemcpy(&bits, net.auditMax, 4, hipMemcpyDeviceToHost));
+    float m;
+    memcpy(&m, &bits, 4);
+    net.auditSeen = std::max(net.auditSeen, m);
+    if(!(net.auditSeen <= auditTol_) && net.nn->precision() == NN_CORRECTED && nnPath_ == NN_DEFAULT) {
+      // the corrected instance missed the default precision's bound on self-play positions:
+      // the same model on the accurate instance from here on (this net's cached evaluations cleared)
+      net.nn.reset(new NNEngine(*net.model, xLen_, yLen_, winLen_, NN_ACCURATE));
+      net.auditSwitches++;
+      const int cap = nnCapFor(hd_.G);
+      if(cap != hd_.nnCap) {
+        hd_.nnCap = cap;
+        KC_HIP(hipMemcpy(&dd_->nnCap, &cap, sizeof(int), hipMemcpyHostToDevice));
+      }
+      if(hd_.cacheOn)
+        KC_HIP(hipMemsetAsync(n ? hd_.cKey1 : hd_.cKey, 0, sizeof(uint64_t) * 2 * ((size_t)hd_.cacheMask + 1),
+                              stream_));
+      KC_HIP(hipStreamSynchronize(stream_));
     }
-    if(hd_.cacheOn)
-      KC_HIP(hipMemsetAsync(hd_.cKey, 0, sizeof(uint64_t) * 2 * ((size_t)hd_.cacheMask + 1), stream_));
-    KC_HIP(hipStreamSynchronize(stream_));
   }
 }
 
@@ -464,16 +552,44 @@ void SelfplayEngine::stats(coffee_selfplay_stats& out) {
   KC_HIP(hipMemcpy(&gdrop, hd_.gDropped, 8, hipMemcpyDeviceToHost));
   out.games_dropped = gdrop;
   out.edge_pool_cap = (uint64_t)hd_.edgePoolCap;
-  out.nn_precision = nn_ ? (uint64_t)nn_->precision() : 0;
-  out.nn_audits = audits_;
-  out.nn_audit_switches = (uint64_t)auditSwitches_;
-  out.nn_audit_max_diff = auditSeen_;
+  out.nn_precision = nets_[0].nn ? (uint64_t)nets_[0].nn->precision() : 0;
+  out.nn_audits = nets_[0].audits;
+  out.nn_audit_switches = (uint64_t)nets_[0].auditSwitches;
+  out.nn_audit_max_diff = nets_[0].auditSeen;
   if(out.errors)
     throw InternalError("self-play device invariant violated in " + std::to_string(out.errors) +
                         " game slot(s): " + std::to_string(out.errors_node_pool) + " node pool exhausted, " +
                         std::to_string(out.errors_edge_pool) + " edge pool exhausted, " +
                         std::to_string(out.errors - out.errors_node_pool - out.errors_edge_pool) +
                         " without a move candidate (raise node_cap)");
+}
+
+void SelfplayEngine::matchStats(coffee_match_stats& out) {
+  if(!hd_.matchMode)
+    throw std::invalid_argument("not a match engine");
+  coffee_selfplay_stats s;
+  stats(s);  // throws on a device error, as for self-play
+  memset(&out, 0, sizeof(out));
+  out.rounds = s.rounds;
+  out.playouts = s.playouts;
+  out.moves = s.moves;
+  out.games_finished = s.games_finished;
+  out.games_dropped = s.games_dropped;
+  out.errors = s.errors;
+  // evaluations per net: the rows kCompact listed for the two launches (the games' own
+  // counters do not say which net answered)
+  int32_t peak[2] = {0, 0};
+  unsigned long long evals[2] = {0, 0};
+  KC_HIP(hipMemcpy(peak, hd_.nnPeak, sizeof(peak), hipMemcpyDeviceToHost));
+  KC_HIP(hipMemcpy(evals, hd_.nnNetEvals, sizeof(evals), hipMemcpyDeviceToHost));
+  for(int n = 0; n < 2; n++) {
+    out.nn_evals[n] = evals[n];
+    out.nn_batch_peak[n] = (uint64_t)peak[n];
+    out.nn_precision[n] = nets_[n].nn ? (uint64_t)nets_[n].nn->precision() : 0;
+    out.nn_audits[n] = nets_[n].audits;
+    out.nn_audit_switches[n] = (uint64_t)nets_[n].auditSwitches;
+    out.nn_audit_max_diff[n] = nets_[n].auditSeen;
+  }
 }
 
 int SelfplayEngine::drain(int maxRows, uint8_t* bin, float* glob, int16_t* pol, float* gt, int8_t* val,
@@ -549,14 +665,16 @@ int SelfplayEngine::drainGames(int maxGames, int32_t* header, uint8_t* moves) {
   if(n > 0) {
     std::vector<GameRec> recs(n);
     KC_HIP(hipMemcpy(recs.data(), hd_.gRec, sizeof(GameRec) * n, hipMemcpyDeviceToHost));
-    const int A = hd_.A;
+    const int A = hd_.A, hw = hd_.matchMode ? 5 : 4;
     for(int i = 0; i < n; i++) {
       const GameRec& r = recs[i];
       if(header) {
-        header[4 * i + 0] = r.slot;
-        header[4 * i + 1] = r.gameNum;
-        header[4 * i + 2] = r.numMoves;
-        header[4 * i + 3] = r.winner;
+        header[hw * i + 0] = r.slot;
+        header[hw * i + 1] = r.gameNum;
+        header[hw * i + 2] = r.numMoves;
+        header[hw * i + 3] = r.winner;
+        if(hd_.matchMode)
+          header[hw * i + 4] = r.candidate;
       }
       if(moves)
         for(int t = 0; t < A; t++) {
@@ -581,21 +699,26 @@ int SelfplayEngine::drainGames(int maxGames, int32_t* header, uint8_t* moves) {
 int SelfplayEngine::nnCapFor(int G) const {
   if(userCap_ > 0)
     return userCap_;
-  if(!nn_)
-    return std::min(G, cus_ * NN_BOARDS_PER_WG);
-  if(!nn_->fused())
-    return G;
-  return std::min(G, nn_->batchCap(cus_, enginesPerDevice_));
+  // (match play: the smaller of the two nets' own caps, on both nets' rows together)
+  int cap = G;
+  for(int n = 0; n < numNets_; n++) {
+    const std::unique_ptr<NNEngine>& nn = nets_[n].nn;
+    if(!nn)
+      cap = std::min(cap, cus_ * NN_BOARDS_PER_WG);
+    else if(nn->fused())
+      cap = std::min(cap, nn->batchCap(cus_, enginesPerDevice_));
+  }
+  return cap;
 }
 
 void SelfplayEngine::setModel(const char* path) {
-  if(!nn_)
+  if(!nets_[0].nn || hd_.matchMode)
     throw std::invalid_argument("engine runs the stand-in network (use_fake_net)");
   switchModel(loadModel(path));  // throws on a bad file; the current network stays
 }
 
 void SelfplayEngine::setModelBytes(const void* data, size_t bytes) {
-  if(!nn_)
+  if(!nets_[0].nn || hd_.matchMode)
     throw std::invalid_argument("engine runs the stand-in network (use_fake_net)");
   switchModel(loadModelBytes(data, bytes, "<model bytes>"));
 }
@@ -604,11 +727,11 @@ void SelfplayEngine::switchModel(const ModelHost& m) {
   std::unique_ptr<NNEngine> next(new NNEngine(m, xLen_, yLen_, winLen_, nnPath_));
   std::unique_ptr<ModelHost> keep(new ModelHost(m));
   sync();
-  nn_ = std::move(next);
-  model_ = std::move(keep);
+  nets_[0].nn = std::move(next);
+  nets_[0].model = std::move(keep);
   // the audit starts over for the new model
-  auditSeen_ = 0.0f;
-  KC_HIP(hipMemset(auditMax_, 0, 4));
+  nets_[0].auditSeen = 0.0f;
+  KC_HIP(hipMemset(nets_[0].auditMax, 0, 4));
   // a reload may change the network path (fused <-> layered) and with it the default cap
   const int cap = nnCapFor(hd_.G);
   if(cap != hd_.nnCap) {

@@ -1,4 +1,5 @@
-// Host self-play engine (selfplay.cpp) behind coffee_selfplay_*.
+// Host self-play engine (selfplay.cpp) behind coffee_selfplay_*, and the same engine in
+// two-network match mode behind coffee_match_*.
 #pragma once
 #include <functional>
 #include <memory>
@@ -11,15 +12,23 @@
 namespace kc {
 
 SP toSP(const coffee_search_params& p);
+// Checks a match config without touching the device (throws std::invalid_argument naming
+// the offending setting): geometry, and the settings match play rejects because they keep
+// a tree across moves or exist only to make training rows.
+void validateMatchConfig(const coffee_match_config& c);
 
 class SelfplayEngine {
  public:
-  explicit SelfplayEngine(const coffee_selfplay_config& c);
+  explicit SelfplayEngine(const coffee_selfplay_config& c) : SelfplayEngine(c, nullptr) {}
+  // Match mode: net 0 (baseline) against net 1 (candidate); a NULL model path is the stand-in
+  explicit SelfplayEngine(const coffee_match_config& c);
   ~SelfplayEngine();
   void step(int rounds, hipStream_t st);
   void sync();
   void stats(coffee_selfplay_stats& out);
+  void matchStats(coffee_match_stats& out);
   int drain(int maxRows, uint8_t* bin, float* glob, int16_t* pol, float* gt, int8_t* val, int32_t* meta);
+  // header [g][4]; match mode [g][5], the candidate's colour last
   int drainGames(int maxGames, int32_t* header, uint8_t* moves);
   // Stream-ordered row hand-off (no host synchronisation): packs every pending row into
   // dst (device, >= rowCap rows), their count into *countOut (host, valid once the
@@ -40,7 +49,7 @@ class SelfplayEngine {
   void kernelTime(int which, double& ms, uint64_t& launches);
   uint64_t timedNNEvals();
   const SearchDev& dev() const { return hd_; }
-  bool nnFused() const { return nn_ && nn_->fused(); }
+  bool nnFused() const { return nets_[0].nn && nets_[0].nn->fused(); }
 
  private:
   struct PendingTiming {
@@ -55,8 +64,26 @@ class SelfplayEngine {
   void resolveTiming();
   std::vector<PendingTiming> pending_;
   std::vector<hipEvent_t> evPool_;
+  // matchPaths: the two model paths of match mode (self-play: nullptr)
+  SelfplayEngine(const coffee_selfplay_config& c, const char* const* matchPaths);
+  static coffee_selfplay_config matchBase(const coffee_match_config& c);
   const DTables* T_ = nullptr;
-  std::unique_ptr<NNEngine> nn_;
+  // Per-network state: self-play holds one network, match play two (each resolves its
+  // precision and runs its audit on its own batches).
+  struct Net {
+    std::unique_ptr<NNEngine> nn;      // null: the stand-in network
+    std::unique_ptr<ModelHost> model;  // the network's model (rebuilt on an audit switch)
+    float* auditOut = nullptr;         // device [G][P+4]: the accurate instance's rows
+    unsigned* auditMax = nullptr;      // device: largest difference so far (float bits)
+    uint64_t nnLaunches = 0;
+    uint64_t audits = 0;
+    float auditSeen = 0.0f;            // largest difference read back so far
+    int auditSwitches = 0;
+  };
+  Net nets_[2];
+  int numNets_ = 1;
+  // one network launch (and its audit, when due) of net n on the list idx / count
+  void forwardNet(int n, const int32_t* count, const int32_t* idx, hipStream_t st, hipEvent_t a, hipEvent_t b);
   SearchDev hd_;
   SearchDev* dd_ = nullptr;
   std::vector<void*> owned_;
@@ -96,15 +123,8 @@ class SelfplayEngine {
   // only at those host synchronisation points, so runs stay reproducible.
   // COFFEE_NN_AUDIT_EVERY (0 = off) and COFFEE_NN_AUDIT_TOL override the defaults.
   void auditCheck();
-  std::unique_ptr<ModelHost> model_;  // the network's model (rebuilt on an audit switch)
-  float* auditOut_ = nullptr;         // device [G][P+4]: the accurate instance's rows
-  unsigned* auditMax_ = nullptr;      // device: largest difference so far (float bits)
   int auditEvery_ = 128;
   float auditTol_ = NNEngine::NN_AUTO_TOL;
-  uint64_t nnLaunches_ = 0;
-  uint64_t audits_ = 0;
-  float auditSeen_ = 0.0f;            // largest difference read back so far
-  int auditSwitches_ = 0;
 };
 
 }  // namespace kc
