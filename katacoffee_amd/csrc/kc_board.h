@@ -18,37 +18,59 @@ KC_HD int dirDy(int d) { return d == 1 ? 0 : -1; }
 // Stones of one colour, chosen by an opaque mask rather than by indexing
 // stones[]: an index (or a select the optimizer turns into one) would force
 // the whole board out of registers into scratch memory.
+//
+// Every function below that takes W1 has a one-word form (W1 = true) for geometries
+// with at most 64 cells, where no high word is ever set: it reads and writes only `lo`.
+// The callers that know the geometry at compile time (the search kernels, by their
+// items-per-lane instance) pass it; everything else, the host included, uses the
+// general two-word form.
+template <bool W1 = false>
 KC_HD BB stonesOf(const DBoard& b, bool white) {
   uint64_t m = white ? ~0ULL : 0ULL;
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" : "+v"(m));
 #endif
-  return BB{(b.stones[0].lo & ~m) | (b.stones[1].lo & m), (b.stones[0].hi & ~m) | (b.stones[1].hi & m)};
+  if constexpr(W1)
+    return BB{(b.stones[0].lo & ~m) | (b.stones[1].lo & m), 0};
+  else
+    return BB{(b.stones[0].lo & ~m) | (b.stones[1].lo & m), (b.stones[0].hi & ~m) | (b.stones[1].hi & m)};
 }
 
-KC_HD BB occupied(const DBoard& b) { return bbOr(b.stones[0], b.stones[1]); }
+template <bool W1 = false>
+KC_HD BB occupied(const DBoard& b) {
+  if constexpr(W1)
+    return BB{b.stones[0].lo | b.stones[1].lo, 0};
+  else
+    return bbOr(b.stones[0], b.stones[1]);
+}
+template <bool W1 = false>
 KC_HD int colorAt(const DBoard& b, int c) {
-  return bbTest(b.stones[0], c) ? 1 : (bbTest(b.stones[1], c) ? 2 : 0);
+  return bbTestW<W1>(b.stones[0], c) ? 1 : (bbTestW<W1>(b.stones[1], c) ? 2 : 0);
 }
 
+template <bool W1 = false>
 KC_HD bool isLegal(const DTables& T, const DBoard& b, int cell, int dir) {
-  BB occ = occupied(b);
-  if(bbTest(occ, cell))
+  BB occ = occupied<W1>(b);
+  if(bbTestW<W1>(occ, cell))
     return false;
-  if(b.lastCell >= 0 && b.lastDir < 4 && !bbTest(T.lineMask[b.lastCell][b.lastDir], cell))
+  if(b.lastCell >= 0 && b.lastDir < 4 && !bbTestW<W1>(T.lineMask[b.lastCell][b.lastDir], cell))
     return false;
-  return bbAny(bbAndNot(T.lineMask[cell][dir], occ));
+  if constexpr(W1)
+    return (T.lineMask[cell][dir].lo & ~occ.lo) != 0;
+  else
+    return bbAny(bbAndNot(T.lineMask[cell][dir], occ));
 }
 
+template <bool W1 = false>
 KC_HD int maxRun(const DTables& T, const DBoard& b, int cell) {
   const int X = T.X, Y = T.Y;
-  const BB own = stonesOf(b, colorAt(b, cell) == 2);
+  const BB own = stonesOf<W1>(b, colorAt<W1>(b, cell) == 2);
   int x = cell % X, y = cell / X, best = 1;
   for(int d = 0; d < 4; d++) {
     int n = 1;
     for(int s = -1; s <= 1; s += 2) {
       int cx = x + s * dirDx(d), cy = y + s * dirDy(d);
-      while(cx >= 0 && cx < X && cy >= 0 && cy < Y && bbTest(own, cy * X + cx)) {
+      while(cx >= 0 && cx < X && cy >= 0 && cy < Y && bbTestW<W1>(own, cy * X + cx)) {
         n++;
         cx += s * dirDx(d);
         cy += s * dirDy(d);
@@ -60,15 +82,16 @@ KC_HD int maxRun(const DTables& T, const DBoard& b, int cell) {
 }
 
 // Longest run of the cell's colour along axis d through the cell (0 if empty).
+template <bool W1 = false>
 KC_HD int runAlong(const DTables& T, const DBoard& b, int cell, int d) {
-  int col = colorAt(b, cell);
+  int col = colorAt<W1>(b, cell);
   if(col == 0)
     return 0;
-  const BB own = stonesOf(b, col == 2);
+  const BB own = stonesOf<W1>(b, col == 2);
   int x = cell % T.X, y = cell / T.X, n = 1;
   for(int s = -1; s <= 1; s += 2) {
     int cx = x + s * dirDx(d), cy = y + s * dirDy(d);
-    while(cx >= 0 && cx < T.X && cy >= 0 && cy < T.Y && bbTest(own, cy * T.X + cx)) {
+    while(cx >= 0 && cx < T.X && cy >= 0 && cy < T.Y && bbTestW<W1>(own, cy * T.X + cx)) {
       n++;
       cx += s * dirDx(d);
       cy += s * dirDy(d);
@@ -93,12 +116,13 @@ KC_HD void boardInit(const DTables& T, DBoard& b) {
 }
 
 // State part of playMove (everything except the end-of-game test).
+template <bool W1 = false>
 KC_HD void applyMove(const DTables& T, DBoard& b, int cell, int dir) {
   int pla = b.pla;
   if(pla == 2)
-    bbSet(b.stones[1], cell);
+    bbSetW<W1>(b.stones[1], cell);
   else
-    bbSet(b.stones[0], cell);
+    bbSetW<W1>(b.stones[0], cell);
   b.h0 ^= T.zBoard[cell][pla][0];
   b.h1 ^= T.zBoard[cell][pla][1];
   b.lastCell = cell;
@@ -147,20 +171,22 @@ KC_HD void stateHash(const DTables& T, const DBoard& b, uint64_t& k0, uint64_t& 
 }
 
 // Wave-cooperative: every lane calls with the same board; result is uniform.
+template <bool W1 = false>
 KC_D bool hasAnyLegalWave(const DTables& T, const DBoard& b) {
   bool any = false;
   for(int pos = laneId(); pos < T.P; pos += 64)
-    any = any || isLegal(T, b, pos % T.A, pos / T.A);
+    any = any || isLegal<W1>(T, b, pos % T.A, pos / T.A);
   return ballot(any) != 0;
 }
 
+template <bool W1 = false>
 KC_D void playMoveWave(const DTables& T, DBoard& b, int cell, int dir) {
   int mover = b.pla;
-  applyMove(T, b, cell, dir);
-  if(maxRun(T, b, cell) >= T.W) {
+  applyMove<W1>(T, b, cell, dir);
+  if(maxRun<W1>(T, b, cell) >= T.W) {
     b.finished = 1;
     b.winner = mover;
-  } else if(!hasAnyLegalWave(T, b)) {
+  } else if(!hasAnyLegalWave<W1>(T, b)) {
     b.finished = 1;
     b.winner = 0;
   }
@@ -168,8 +194,9 @@ KC_D void playMoveWave(const DTables& T, DBoard& b, int cell, int dir) {
 
 // The 15 V1 feature bits of ORIGINAL cell c (bit p = plane p); sd0 is the
 // symmetric direction of the last move (-1 when there is none).
+template <bool W1 = false>
 KC_D uint32_t v1CellFeatures(const DTables& T, const DBoard& b, int c, int sd0) {
-  const int col = colorAt(b, c);
+  const int col = colorAt<W1>(b, c);
   uint32_t f = 1u;
   if(col != 0)
     f |= col == b.pla ? 2u : 4u;
@@ -181,8 +208,8 @@ KC_D uint32_t v1CellFeatures(const DTables& T, const DBoard& b, int c, int sd0) 
       f |= 1u << (6 + k);
   bool legal = false, run[3] = {false, false, false};
   for(int d = 0; d < 4; d++) {
-    legal = legal || isLegal(T, b, c, d);
-    const int n = runAlong(T, b, c, d);
+    legal = legal || isLegal<W1>(T, b, c, d);
+    const int n = runAlong<W1>(T, b, c, d);
 #pragma unroll
     for(int j = 0; j < 3; j++)
       run[j] = run[j] || (n >= 1 && n == T.W - 1 - j);
@@ -199,6 +226,7 @@ KC_D uint32_t v1CellFeatures(const DTables& T, const DBoard& b, int c, int sd0) 
 // Lane s evaluates all 15 features of symmetric cell s (one table lookup, the
 // four axes once), one ballot per plane collects them, and lane w assembles
 // word w from the uniform plane masks.
+template <bool W1 = false>
 KC_D void encodePackedWave(const DTables& T, const DBoard& b, int sym, uint64_t* out) {
   if(T.X != T.Y)
     sym &= 3;
@@ -208,7 +236,7 @@ KC_D void encodePackedWave(const DTables& T, const DBoard& b, int sym, uint64_t*
   uint64_t word = 0;
   for(int base = 0; base < A; base += 64) {
     const int s = base + lane;
-    const uint32_t f = s < A ? v1CellFeatures(T, b, T.invSymCell[sym][s], sd0) : 0u;
+    const uint32_t f = s < A ? v1CellFeatures<W1>(T, b, T.invSymCell[sym][s], sd0) : 0u;
     // plane p's chunk covers flat bits [p*A + base, p*A + base + 64): OR the part
     // falling into this lane's word [64*lane, 64*lane + 64)
 #pragma unroll

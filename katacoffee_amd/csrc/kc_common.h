@@ -51,6 +51,22 @@ KC_HD void bbSet(BB& b, int c) {
   else
     b.hi |= 1ULL << (c - 64);
 }
+// One-word forms for geometries with at most 64 cells (W1): the high word is never
+// set there and c < 64, so only `lo` is read or written.  W1 = false is the general form.
+template <bool W1>
+KC_HD bool bbTestW(const BB& b, int c) {
+  if constexpr(W1)
+    return (b.lo >> c) & 1ULL;
+  else
+    return bbTest(b, c);
+}
+template <bool W1>
+KC_HD void bbSetW(BB& b, int c) {
+  if constexpr(W1)
+    b.lo |= 1ULL << c;
+  else
+    bbSet(b, c);
+}
 KC_HD BB bbOr(const BB& a, const BB& b) { return BB{a.lo | b.lo, a.hi | b.hi}; }
 KC_HD BB bbAnd(const BB& a, const BB& b) { return BB{a.lo & b.lo, a.hi & b.hi}; }
 KC_HD BB bbAndNot(const BB& a, const BB& b) { return BB{a.lo & ~b.lo, a.hi & ~b.hi}; }

@@ -50,7 +50,13 @@ KC_D void waveSync() {
 // 10 backup blocks  11 backup total  12 postprocess+order  13 path backup  14 leaf value
 // 16 commit blocks  17 commit total  18 move choice+targets  19 tree reuse  20 finishGame
 // 21 startGame      22 live nodes kept  23 finished games
-constexpr int SPROF_N = 32;
+// per path level (the profiling build drains the memory counters at each mark, SPROF_WAIT,
+// so a wait is charged to its own slot: the levels' loads overlap less than in the product)
+// 32 descent: wait for the node's record and first edges   33 issue + wait of the children's records
+// 34 descent: selection arithmetic                         35 descent levels
+// 36 backup: wait for the level's loads   37 arithmetic (with the t-CDF reads and the next levels' load issue)
+// 38 backup: stores                       39 backup levels
+constexpr int SPROF_N = 48;
 constexpr int SPROF_MAXG = 16384;
 __device__ unsigned long long g_searchProf[SPROF_MAXG * SPROF_N];
 // NN-cache probe: every evaluated leaf's state key goes into an open-addressing set;
@@ -77,6 +83,7 @@ KC_D unsigned long long* sprofLds() {
   return c;
 }
 #define SPROF_NOW() clock64()
+#define SPROF_WAIT() __builtin_amdgcn_s_waitcnt(0)
 #define SPROF_INIT()                   \
   do {                                 \
     if(laneId() < SPROF_N)             \
@@ -91,7 +98,7 @@ KC_D unsigned long long* sprofLds() {
 #define SPROF_FLUSH()                                                           \
   do {                                                                          \
     __syncthreads();                                                            \
-    if(laneId() < SPROF_N && blockIdx.x < SPROF_MAXG && laneId() < 24)          \
+    if(blockIdx.x < SPROF_MAXG && (laneId() < 24 || (laneId() >= 32 && laneId() < 40))) \
       g_searchProf[blockIdx.x * SPROF_N + laneId()] += sprofLds()[laneId()];    \
   } while(0)
 // per-block maximum of a value over launches (slots 24..31; no contention)
@@ -106,6 +113,9 @@ KC_D unsigned long long* sprofLds() {
   } while(0)
 #else
 #define SPROF_NOW() 0ull
+#define SPROF_WAIT() \
+  do {               \
+  } while(0)
 #define SPROF_INIT() \
   do {               \
   } while(0)
@@ -207,13 +217,10 @@ KC_D int bcastI(int v, int srcLane) { return bcastLane(v, srcLane); }
 
 // Child slots read speculatively with their node record (2 x 128-B lines of Edge).
 constexpr int SPEC_EDGES = INLINE_EDGES;
-// descend(): request the likely next node (most-visited inline child) with the children's
-// records.  A/B switch, off: bit-exact but slower on the C2 bench (kSelect 64.9-65.1 vs
-// 60.3-61.0 us, 23.4 k vs 24.0-24.2 k rows/s, same box: profiles/r05/spec_next_ab.txt) --
-// the argmax sits on the critical path and kSelect<2> spills 7 more registers
-#ifndef KC_SPEC_NEXT
-#define KC_SPEC_NEXT 0
-#endif
+// The board functions' one-word form (kc_board.h) by the kernels' items-per-lane instance:
+// laneItems() gives NI <= 4 only to P = 4 A <= 256, that is A <= 64 cells.
+template <int NI>
+constexpr bool W1_OF = NI <= 4;
 KC_D int firstLane(uint64_t m) { return __builtin_ctzll(m); }
 
 KC_D float childWeight(uint32_t edgeVisits, uint32_t childVisits, float rawWeight) {
@@ -290,6 +297,7 @@ KC_D int svbFindOrInsert(const GV& v, int sel, uint64_t k, uint64_t first) {
 }
 
 // SPEC a19 key (oracle svbKey): Zmove0[parentPrev] ^ Zmove1[move] ^ Zpla[mover] ^ 5x5 pattern.
+template <bool W1 = false>
 KC_D uint64_t svbKeyOf(const GV& v, const DBoard& before, int parentPrevPos, int movePos, int mover) {
   const DTables& T = v.T;
   uint64_t h = 0;
@@ -297,7 +305,7 @@ KC_D uint64_t svbKeyOf(const GV& v, const DBoard& before, int parentPrevPos, int
     int wy = v.lane / 5, wx = v.lane % 5;
     int cell = movePos % T.A;
     int xx = cell % T.X + wx - 2, yy = cell / T.X + wy - 2;
-    int col = (xx >= 0 && xx < T.X && yy >= 0 && yy < T.Y) ? colorAt(before, yy * T.X + xx) : 3;
+    int col = (xx >= 0 && xx < T.X && yy >= 0 && yy < T.Y) ? colorAt<W1>(before, yy * T.X + xx) : 3;
     h = T.svbZ[SVB_IDX_PAT + col * 25 + wy * 5 + wx];
   }
   h = waveXor64(h);
@@ -491,6 +499,13 @@ template <int NI, class F>
 KC_D LevelOut computeLevel(const GV& v, const GameDev& s, PathLevel<NI>& L, const LevelOut& below, bool haveBelow,
                            int numVisitsToAdd, bool isRoot, F&& issueNext) {
   const SP& sp = *v.sp;
+  const unsigned long long tLoads = SPROF_NOW();
+  (void)tLoads;
+  SPROF_WAIT();
+  const unsigned long long tCalc = SPROF_NOW();
+  (void)tCalc;
+  SPROF_ADD(36, tCalc - tLoads);
+  SPROF_ADD(39, 1);
   const int k = L.k, slot = L.slot;
   const int nextPla = L.nextPla;
   const int svbEntry = L.svbEntry;
@@ -673,6 +688,9 @@ KC_D LevelOut computeLevel(const GV& v, const GameDev& s, PathLevel<NI>& L, cons
   out.st.weightSum = weightSum;
   out.st.visits = L.visits0 + (uint32_t)numVisitsToAdd;
   waveSync();
+  const unsigned long long tStore = SPROF_NOW();
+  (void)tStore;
+  SPROF_ADD(37, tStore - tCalc);
   if(v.lane == 0) {
     Node* np = &v.nodes()[L.ni];
     np->winLossAvg = out.st.winLossAvg;
@@ -685,6 +703,7 @@ KC_D LevelOut computeLevel(const GV& v, const GameDev& s, PathLevel<NI>& L, cons
     np->lastSvbWeight = newLastW;
   }
   waveSync();
+  SPROF_ADD(38, SPROF_NOW() - tStore);
   return out;
 }
 
@@ -773,8 +792,7 @@ KC_D float exploreScaling(const SP& sp, float totalChildWeight) {
 // broadcast from the lane that holds them (no reload of either after the choice).
 template <int NI>
 KC_D int selectBest(const GV& v, int ni, const Node& n, const float* pol, bool isRoot, int& newPos,
-                    uint32_t* hasBits, const Edge& e0, Edge& ce, uint32_t& cVisits, uint32_t& cFlags, int* specChild = nullptr,
-                    Edge* specE0 = nullptr, Node* specN = nullptr) {
+                    uint32_t* hasBits, const Edge& e0, Edge& ce, uint32_t& cVisits, uint32_t& cFlags) {
   const SP& sp = *v.sp;
   const int P = v.d.P;
   const int k = n.numChildren;
@@ -784,6 +802,8 @@ KC_D int selectBest(const GV& v, int ni, const Node& n, const float* pol, bool i
       hasBits[w] = 0;
     waveSync();
   }
+  const unsigned long long tKids = SPROF_NOW();
+  (void)tKids;
   const NodeEdges E = v.edges(ni, n.edgeBase);
   const Node* NS = v.nodes();
   float probs[NI], cw[NI], pv[NI], cu[NI];
@@ -812,20 +832,10 @@ KC_D int selectBest(const GV& v, int ni, const Node& n, const float* pol, bool i
         atomicOr(&hasBits[e.move >> 5], 1u << (e.move & 31));
     }
   }
-  if(specChild) {
-    // the next level, speculatively: the inline child with the most edge visits (the
-    // usual pick once a node has visits) -- its record and inline edges are requested
-    // behind the children's records, so a hit saves the next level's first round trip
-    float sv = v.lane < k && v.lane < SPEC_EDGES ? (float)e0.visits : -1.0f;
-    int si = v.lane;
-    waveArgmax(sv, si);
-    const int sc = sv >= 0.0f ? bcastLane((int)e0.child, si) : -1;
-    *specChild = sc;
-    if(sc >= 0) {
-      *specE0 = v.lane < SPEC_EDGES && v.lane < v.d.P ? v.inlineEdges(sc)[v.lane] : Edge{0u, 0u, 0.0f, 0u};
-      *specN = NS[sc];
-    }
-  }
+  SPROF_WAIT();
+  const unsigned long long tArith = SPROF_NOW();
+  (void)tArith;
+  SPROF_ADD(33, tArith - tKids);
   const float probMass = tsum<NI>(probs, k, v.lane);
   const float total = tsum<NI>(cw, k, v.lane);
   const float fpu = fpuValue(sp, n, pla, isRoot, probMass);
@@ -906,6 +916,7 @@ KC_D int selectBest(const GV& v, int ni, const Node& n, const float* pol, bool i
       newPos = bpos;
     }
   }
+  SPROF_ADD(34, SPROF_NOW() - tArith);
   return bestSlot;
 }
 
@@ -938,15 +949,9 @@ KC_D void nextExpansion(const GV& v, const float (&pv)[NI], float curPrior, int 
 
 // oracle descend (playoutDescend search.cpp:936-1165, allocateOrFindNode :704-759,
 // maybeCatchUpEdgeVisits :1169-1207)
-// KC_TT_EARLY 1: an expansion that lands on a transposition requests the child's record
-// right after the table probe; 0: after the edge and node stores.  Measured (round 6, C2
-// fast, 4 groups, profiles/r06/tt_early_ab.txt): 25.81 / 25.84 k rows/s early against
-// 25.97 / 25.94 k late, bit-exact either way: off
-#ifndef KC_TT_EARLY
-#define KC_TT_EARLY 0
-#endif
 template <int NI>
 KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* LDS [P] */) {
+  constexpr bool W1 = W1_OF<NI>;
   const SP& sp = *v.sp;
   const DTables& T = v.T;
   s.pathLen = 0;
@@ -983,6 +988,13 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
     waveSync();
   }
   while(true) {
+    {
+      const unsigned long long tw = SPROF_NOW();
+      (void)tw;
+      SPROF_WAIT();
+      SPROF_ADD(32, SPROF_NOW() - tw);
+      SPROF_ADD(35, 1);
+    }
     if(n.flags & 2) {
       s.leafKind = LEAF_TERMINAL;
       s.leafNode = ni;
@@ -996,12 +1008,11 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
     const unsigned long long tSel = SPROF_NOW();
     Edge ce{0u, 0u, 0.0f, 0u};
     uint32_t cVisits = 0, cFlags = 0;
-    int specChild = -1;
-    Edge specE0{0u, 0u, 0.0f, 0u};
-    Node specN;
-    int slot = KC_SPEC_NEXT ? selectBest<NI>(v, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags, &specChild,
-                                             &specE0, &specN)
-                            : selectBest<NI>(v, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags);
+    // a node with at most 64 children (every non-root level in practice, the root until
+    // its 65th child) takes the one-item form: an empty second item adds nothing to the
+    // sums and never wins the (value, index) argmax, so the results are the same
+    int slot = n.numChildren <= 64 ? selectBest<1>(v, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags)
+                                   : selectBest<NI>(v, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags);
     SPROF_ADD(5, SPROF_NOW() - tSel);
     (void)tSel;
     if(slot < 0) {
@@ -1058,24 +1069,15 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
       const bool svbKeyed = sp.svbFactor != 0.0f && hCell(b, 0) >= 0;
       uint64_t svbKey = 0, svbFirst = 0;
       if(svbKeyed) {
-        svbKey = svbKeyOf(v, b, hDir(b, 0) * T.A + hCell(b, 0), newPos, b.pla);
+        svbKey = svbKeyOf<W1>(v, b, hDir(b, 0) * T.A + hCell(b, 0), newPos, b.pla);
         svbFirst = svbProbe(v, s.svbSel, svbKey);
       }
-      playMoveWave(T, b, cell, dir);
+      playMoveWave<W1>(T, b, cell, dir);
       uint64_t k0, k1;
       stateHash(T, b, k0, k1);
       int ttSlot = -1;
       int child = sp.useGraph ? ttFind(v, k0, k1, ttSlot) : -1;
       const bool fresh = child < 0;
-      // a transposition's record (visits, terminal flag) is requested here, so its latency
-      // overlaps the next-candidate scan and the stores below; nothing in this descent
-      // writes it (a child always holds more stones than its parent: never ni)
-      uint32_t tVisits = 0u, tFlags = 0u;
-      if(KC_TT_EARLY && !fresh) {
-        const Node& cn = v.nodes()[child];
-        tVisits = cn.visits;
-        tFlags = (uint32_t)cn.flags;
-      }
       float nxtPrior = -1.0f;
       int nxtPos = 0xFFFF;
       if(!isRoot)
@@ -1114,8 +1116,8 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
       SPROF_ADD(6, SPROF_NOW() - tExp);
       // a fresh node has no visits and the terminal flag of b; a transposition's
       // record is read
-      const uint32_t cv = fresh ? 0u : (KC_TT_EARLY ? tVisits : v.nodes()[child].visits);
-      const uint32_t cf = fresh ? (b.finished ? 2u : 0u) : (KC_TT_EARLY ? tFlags : (uint32_t)v.nodes()[child].flags);
+      const uint32_t cv = fresh ? 0u : v.nodes()[child].visits;
+      const uint32_t cf = fresh ? (b.finished ? 2u : 0u) : (uint32_t)v.nodes()[child].flags;
       if(cv > 0) {
         s.leafKind = LEAF_CATCHUP;
         s.leafNode = child;
@@ -1139,21 +1141,14 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
     }
     // existing child: its terminal flag already says whether the move ends the game
     const int mv = (int)ce.move, mover = b.pla;
-    applyMove(T, b, mv % T.A, mv / T.A);
+    applyMove<W1>(T, b, mv % T.A, mv / T.A);
     if(cFlags & 2) {
       b.finished = 1;
-      b.winner = maxRun(T, b, mv % T.A) >= T.W ? mover : 0;
+      b.winner = maxRun<W1>(T, b, mv % T.A) >= T.W ? mover : 0;
     }
     ni = child;
-    if(KC_SPEC_NEXT && child == specChild) {
-      // (no node or edge is written before a descent's last level: the speculative
-      // copies are what the loads would return)
-      e0 = specE0;
-      n = specN;
-    } else {
-      e0 = loadE0(ni);
-      n = v.nodes()[ni];
-    }
+    e0 = loadE0(ni);
+    n = v.nodes()[ni];
   }
   s.treeLevels += (uint64_t)s.pathLen;
   s.treeChildren += scanned;
@@ -1233,6 +1228,7 @@ KC_D void cacheLookup(const GV& v, GameDev& s, bool fused) {
 
 // The end of a selection: an NN leaf draws its symmetry, the game's batch row is encoded
 // when the leaf needs the network, and the game state is stored.
+template <bool W1>
 KC_D void finishSelect(const GV& v, GameDev& s, DRng& rng) {
   const SearchDev& d = v.d;
   const int g = v.g;
@@ -1253,7 +1249,7 @@ KC_D void finishSelect(const GV& v, GameDev& s, DRng& rng) {
     const int slot = g;
     s.nnSlot = slot;
     s.nnEvals++;
-    encodePackedWave(v.T, s.leaf, s.leafSym, d.nnIn + (size_t)slot * d.inWords);
+    encodePackedWave<W1>(v.T, s.leaf, s.leafSym, d.nnIn + (size_t)slot * d.inWords);
   }
   waveSync();
   storeGame(v, s);
@@ -1341,7 +1337,7 @@ KC_D void selectBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   }
   const unsigned long long t2 = SPROF_NOW();
   (void)t2;
-  finishSelect(v, s, rng);
+  finishSelect<W1_OF<NI>>(v, s, rng);
   SPROF_ADD(0, 1);
   SPROF_MAX(24, SPROF_NOW() - t0);
   SPROF_MAX(25, s.pathLen);
@@ -1398,7 +1394,7 @@ KC_D void completePending(const SearchDev& d, const DTables& T, int first, int s
     s.leafKind = LEAF_NN;
     cacheLookup<NI>(v, s, false);
     DRng rng = DRng{s.rngSeed, s.rngCtr};
-    finishSelect(v, s, rng);
+    finishSelect<W1_OF<NI>>(v, s, rng);
   }
 }
 template <int NI>
@@ -1435,7 +1431,7 @@ KC_D void postprocess(const GV& v, const DBoard& b, int sym, const float* out, f
     src[j] = 0;
     if(pos < P) {
       const int dd = pos / A, cell = pos % A;
-      legal[j] = isLegal(T, b, cell, dd);
+      legal[j] = isLegal<W1_OF<NI>>(T, b, cell, dd);
       src[j] = T.symDir[sym][dd] * A + T.symCell[sym][cell];
     }
   }
@@ -1684,25 +1680,36 @@ KC_D bool initMove(const GV& v, GameDev& s, const float* o, float* scratch /* LD
   return false;
 }
 
-// One game's backup; returns whether s holds the game's state afterwards (fused: not yet
-// stored -- selectBody stores it on every path).
-// fused (kBackupSelect): a cache-slot winner leaves the slot's tag set -- the selections
-// running beside it treat the slot as being written -- and kResolve clears it.
-template <int NI, bool MATCH = false>
-KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bool fused, float* scratch) {
-  if(d.nnDefer[g])  // a deferred leaf is backed up in a later round
-    return false;
-  GV v(d, T, g);
-  SPROF_INIT();
-  const unsigned long long t0 = SPROF_NOW();
-  (void)t0;
-  loadGame(v, s);
-  if(s.leafKind == LEAF_NONE)
-    return true;
-  unsigned long long tPost = 0, tLeaf = 0, tPath = 0;
-  (void)tPost;
-  (void)tLeaf;
-  (void)tPath;
+// The evaluations that are not playouts -- a policy-initialisation move, a fork candidate,
+// a side position, one symmetry of a root evaluation (a few per move against hundreds of
+// playouts) -- run out of line: the round kernels' straight line and register allocation
+// do not carry them.  Arguments by value; the game's state goes through its LDS copy *gs
+// (the fences order this function's generic-pointer accesses to it against the caller's).
+// Returns whether the game is due for a commit.
+template <class T>
+KC_D T* uniformPtr(T* p) {  // a function's arguments arrive per lane: back to a scalar
+  const uint64_t x = (uint64_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)(x >> 32));
+  return (T*)(((uint64_t)hi << 32) | lo);
+}
+// A uniform pointer to a structure no kernel writes (SearchDev, DTables), as a constant-
+// address-space pointer: its uniform reads stay scalar loads inside a called function, as
+// they are through the kernels' readonly arguments (asGlobal in search.h needs them so).
+template <class T>
+KC_D const T* uniformConst(const T* p) {
+  const __attribute__((address_space(4))) T* q = (const __attribute__((address_space(4))) T*)uniformPtr(p);
+  asm volatile("" : "+s"(q));
+  return (const T*)q;
+}
+template <int NI>
+__device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, int g, GameDev* gs, float* scratch) {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  const SearchDev& d = *uniformConst(dp);
+  GameDev& s = *uniformPtr(gs);
+  scratch = uniformPtr(scratch);
+  g = __builtin_amdgcn_readfirstlane(g);
+  GV v(d, *uniformConst(Tp), g);
+  bindGame(v, s);
   const SP& sp = *v.sp;
   const int P = d.P;
   const float* o = d.nnOut + (size_t)s.nnSlot * (P + 4);
@@ -1713,7 +1720,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
     forkEval<NI>(v, s, o, scratch);
   } else if(s.leafKind == LEAF_SIDE) {
     sideEval<NI>(v, s, o, scratch);
-  } else if(s.leafKind == LEAF_ROOTEVAL) {
+  } else {
     float* pol = scratch;
     float w, l;
     float pv[NI];
@@ -1765,6 +1772,36 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
       s.phase = PH_SEARCH;
       needCommit = v.nodes()[s.rootIdx].visits >= (uint32_t)s.visitLimit;
     }
+  }
+  waveSync();
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  return needCommit;
+}
+
+// One game's backup; returns whether s holds the game's state afterwards (fused: not yet
+// stored -- selectBody stores it on every path).
+// fused (kBackupSelect): a cache-slot winner leaves the slot's tag set -- the selections
+// running beside it treat the slot as being written -- and kResolve clears it.
+template <int NI, bool MATCH = false>
+KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bool fused, float* scratch) {
+  if(d.nnDefer[g])  // a deferred leaf is backed up in a later round
+    return false;
+  GV v(d, T, g);
+  SPROF_INIT();
+  const unsigned long long t0 = SPROF_NOW();
+  (void)t0;
+  loadGame(v, s);
+  if(s.leafKind == LEAF_NONE)
+    return true;
+  unsigned long long tPost = 0, tLeaf = 0, tPath = 0;
+  (void)tPost;
+  (void)tLeaf;
+  (void)tPath;
+  const int P = d.P;
+  const float* o = d.nnOut + (size_t)s.nnSlot * (P + 4);
+  bool needCommit = false;
+  if(s.leafKind == LEAF_INIT || s.leafKind == LEAF_FORK || s.leafKind == LEAF_SIDE || s.leafKind == LEAF_ROOTEVAL) {
+    needCommit = rareLeaf<NI>(&d, &T, g, &s, scratch);
   } else {
     NStats leafSt{0u, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     bool haveLeaf = false;
@@ -1867,13 +1904,16 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
 
 template <int NI, bool MATCH = false>
 __global__ void __launch_bounds__(64, NI <= 4 ? 4 : 3) kBackup(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp) {
-  const SearchDev& d = *dp;
+  // (constant views: the call to rareLeaf does not count as a write to *dp or *Tp, so
+  // their uniform reads after it stay scalar loads)
+  const SearchDev& d = *uniformConst(dp);
+  const DTables& T = *uniformConst(Tp);
   const int g = blockIdx.x;
   if(g >= d.G)
     return;
   __shared__ __attribute__((aligned(16))) float scratch[3 * MAX_P];
   __shared__ GameDev s;
-  backupBody<NI, MATCH>(d, *Tp, g, s, false, scratch);
+  backupBody<NI, MATCH>(d, T, g, s, false, scratch);
 }
 
 // Round r's backup and round r+1's selection of one game in one kernel (no commit between
@@ -1888,26 +1928,20 @@ __global__ void __launch_bounds__(64, NI <= 4 ? 4 : 3) kBackup(const SearchDev* 
 #ifndef KC_FUSED_OCC
 #define KC_FUSED_OCC 4
 #endif
-// A/B switch: KC_SEARCH_PRIO > 0 raises the fused search waves' issue priority (s_setprio)
-// over the other group's network waves sharing their SIMD
-#ifndef KC_SEARCH_PRIO
-#define KC_SEARCH_PRIO 0
-#endif
 template <int NI>
 __global__ void __launch_bounds__(64, NI <= 2 ? KC_FUSED_OCC : 2) kBackupSelect(const SearchDev* __restrict__ dp,
                                                                       const DTables* __restrict__ Tp) {
-  const SearchDev& d = *dp;
+  const SearchDev& d = *uniformConst(dp);  // constant views: see kBackup
+  const DTables& T = *uniformConst(Tp);
   const int g = blockIdx.x;
   if(g >= d.G)
     return;
-  if constexpr(KC_SEARCH_PRIO > 0)
-    __builtin_amdgcn_s_setprio(KC_SEARCH_PRIO);
   __shared__ __attribute__((aligned(16))) float scratch[3 * MAX_P];
   __shared__ uint32_t hasBits[(MAX_P + 31) / 32];
   __shared__ GameDev s;
-  const bool loaded = backupBody<NI>(d, *Tp, g, s, true, scratch);
+  const bool loaded = backupBody<NI>(d, T, g, s, true, scratch);
   // (the selection's root policy reuses the backup's scratch)
-  selectBody<NI>(d, *Tp, g, s, loaded, true, hasBits, scratch);
+  selectBody<NI>(d, T, g, s, loaded, true, hasBits, scratch);
 }
 
 #ifdef KC_SEARCH_PROFILE
@@ -1930,7 +1964,7 @@ extern "C" void coffee_debug_search_profile(unsigned long long* out, int reset) 
     out[i] = 0;
   for(size_t k = 0; k < all.size(); k++) {
     const int i = (int)(k % SPROF_N);
-    if(i < 24)
+    if(i < 24 || i >= 32)
       out[i] += all[k];
     else if(i <= 26)
       out[i] = std::max(out[i], all[k]);

@@ -23,7 +23,7 @@ def main():
     a = ap.parse_args()
     import katacoffee_amd as kc
     L = kc.lib()
-    prof = (ctypes.c_ulonglong * 32)()
+    prof = (ctypes.c_ulonglong * 48)()
     path = os.path.join(tempfile.mkdtemp(), "m.cfnn")
     kc.write_random_model("b6c96", 0xC0FFEE, path)
     sp = kc.Selfplay(5, 5, 4, num_games=a.games, max_visits=a.visits, seed=1, model_path=path, commit_interval=8,
@@ -45,6 +45,10 @@ def main():
                     ("encode+slot", 7)]:
         print("  %-14s %8.0f cycles/block" % (name, p[i] / nb))
     print("  path levels    %8.2f per block" % (p[4] / nb))
+    nl = max(p[35], 1)
+    print("  per level (%.2f levels entered per block; the marks drain the memory counters):" % (p[35] / nb))
+    for name, i in [("wait node+edges", 32), ("kids issue+wait", 33), ("arithmetic", 34)]:
+        print("    %-16s %8.0f cycles/level" % (name, p[i] / nl))
     print("  slowest select block %d cycles (mean of per-slot maxima %.0f), deepest path %d" %
           (p[24], p[27] / max(1, a.games), p[25]))
     print("  slowest backup block %d cycles (mean of per-slot maxima %.0f)" % (p[26], p[28] / max(1, a.games)))
@@ -54,6 +58,10 @@ def main():
     print("backup: %d blocks" % p[10])
     for name, i in [("total", 11), ("post+order", 12), ("leaf value", 14), ("path backup", 13)]:
         print("  %-14s %8.0f cycles/block" % (name, p[i] / nk))
+    nl = max(p[39], 1)
+    print("  per level (%.2f levels per block; the marks drain the memory counters):" % (p[39] / nk))
+    for name, i in [("wait for loads", 36), ("arithmetic", 37), ("stores", 38)]:
+        print("    %-16s %8.0f cycles/level" % (name, p[i] / nl))
     nc = max(p[16], 1)
     print("commit: %d blocks, %d finished games, %.0f live nodes kept per move" % (p[16], p[23], p[22] / nc))
     for name, i in [("total", 17), ("choice+targets", 18), ("tree reuse", 19)]:
