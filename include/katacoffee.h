@@ -422,6 +422,122 @@ int coffee_match_game_tree(coffee_match* h, int slot, int max_nodes, uint32_t* n
                            int* n_nodes);
 int coffee_match_root_policy(coffee_match* h, int slot, float* out);
 
+/* ---- batched position analysis (the engine behind the reference's `katago analysis`,
+ *      cpp/command/analysis.cpp, on the self-play engine's round kernels) ----
+ * num_slots concurrent searches.  A slot holds one query or is idle; queries wait in a ring in
+ * device memory, a finished search is turned into a result on the device and its slot takes
+ * the next queued query in the same kernel, so slots never wait for the host.
+ * A query is a move list from the empty board (policy positions dir * A + cell, alternating
+ * from player 1).  The search is the engine's own: a fresh tree, max_visits root visits.
+ * RNG coordinates: the search's stream is seeded from (config seed, stream, game_num) by the
+ * formula self-play uses for (seed, global slot, game number), so a result does not depend on
+ * the slot that searched it; a nonzero rng_counter sets the stream's position (a self-play
+ * game's coffee_selfplay_game_info counter reproduces that game's search of the position).
+ * Values are reported as stored: from WHITE's perspective.  The side to move is `pla`.
+ * Principal variation of a child: its move, then at every node the child with the most edge
+ * visits (ties: lower child slot) until a node without children or a terminal node, at most
+ * max_pv_len moves.  (The reference follows play-selection values instead.)
+ * Settings that keep a tree or exist only to make rows are rejected with COFFEE_EINVAL before
+ * any device call: the list of coffee_match_config plus init_games_with_policy. */
+#define COFFEE_ANALYSIS_MAX_MOVES 100
+#define COFFEE_ANALYSIS_MAX_PV 16
+enum {
+  COFFEE_ANALYSIS_OK = 0,            /* searched: the move records are valid */
+  COFFEE_ANALYSIS_ILLEGAL_MOVE = 1,  /* info = index of the first illegal move */
+  COFFEE_ANALYSIS_GAME_OVER = 2,     /* the move list ends the game: info = winner (0 draw: board full) */
+  COFFEE_ANALYSIS_NO_LEGAL_MOVE = 3  /* the side to move has no legal move (a draw) */
+};
+
+typedef struct coffee_analysis_config {
+  int32_t x, y, win_len;
+  int32_t num_slots;       /* concurrent searches on this device */
+  int32_t node_cap;        /* per-slot node pool; 0 = max(2048, 3*max_visits) */
+  uint64_t seed;
+  const char* model_path;  /* CFNN model, host string; NULL = the stand-in network */
+  coffee_search_params search; /* coffee_analysis_params_default */
+  int32_t nn_cache_log2;   /* as coffee_selfplay_config */
+  int32_t nn_batch_cap;
+  int32_t nn_precision;
+  int32_t engines_per_device;
+  int32_t commit_interval; /* rounds between report launches; 0 = 8 */
+  int32_t query_capacity;  /* >= 1: most queries submitted and not yet drained */
+  int32_t max_pv_len;      /* 0..COFFEE_ANALYSIS_MAX_PV */
+} coffee_analysis_config;
+
+typedef struct coffee_analysis_query {
+  uint64_t id;
+  uint64_t rng_counter;    /* 0 = the stream's position after its two game-hash draws */
+  uint32_t stream, game_num;
+  int32_t num_moves;       /* 0..x*y */
+  int32_t max_visits;      /* 0 = search.max_visits; at most node_cap - 4 */
+  uint16_t moves[COFFEE_ANALYSIS_MAX_MOVES];
+} coffee_analysis_query;
+
+typedef struct coffee_analysis_result {
+  uint64_t id;
+  int32_t status;          /* COFFEE_ANALYSIS_* */
+  int32_t info;
+  int32_t turn, pla;       /* of the analysed position (status 1: of the position before the illegal move) */
+  uint32_t visits;         /* the root's record, bit copies */
+  float weight_sum, utility_avg, win_loss_avg, nn_win, nn_loss;
+  int32_t num_children;
+  int32_t pad;
+} coffee_analysis_result;
+
+typedef struct coffee_analysis_move {  /* one root child, in child-slot order */
+  int32_t move;
+  uint32_t edge_visits;
+  uint32_t visits;         /* the child's record, bit copies */
+  float weight_sum, utility_avg, win_loss_avg;
+  float prior;             /* the root's NN policy of the move, before temperature and noise */
+  float lcb, radius;       /* from the mover's perspective (getSelfUtilityLCBAndRadius) */
+  float play_selection_value;
+  int32_t order;           /* rank by play-selection value descending, ties by lower child slot */
+  int32_t pv_len;
+  uint16_t pv[COFFEE_ANALYSIS_MAX_PV];
+} coffee_analysis_move;
+
+typedef struct coffee_analysis_stats {
+  uint64_t rounds, playouts, nn_evals;
+  uint64_t queries_loaded;   /* queries taken from the ring */
+  uint64_t queries_finished; /* results written */
+  uint64_t queries_rejected; /* of those, answered without a search (status != 0) */
+  uint64_t errors;           /* as coffee_selfplay_stats */
+  uint64_t nn_precision, nn_audits, nn_audit_switches;
+  double nn_audit_max_diff;
+} coffee_analysis_stats;
+
+typedef struct coffee_analysis coffee_analysis;
+
+/* coffee_match_params_default with the values of configs/analysis_example.cfg: 500 visits,
+ * LCB on at 5.0 / 0.15, one root symmetry; root noise off; chosen_move_subtract and
+ * chosen_move_prune 0, so the reported play-selection values are unpruned. */
+void coffee_analysis_params_default(coffee_search_params* p);
+int coffee_analysis_create(const coffee_analysis_config* cfg, coffee_analysis** out);
+/* As coffee_selfplay_step / _sync / _stream / _destroy. */
+int coffee_analysis_step(coffee_analysis* h, int rounds, void* stream);
+int coffee_analysis_sync(coffee_analysis* h);
+int coffee_analysis_stream(coffee_analysis* h, void** stream);
+int coffee_analysis_destroy(coffee_analysis* h);
+/* Copies up to n queries (host) into the device ring without waiting for the engine stream's
+ * work; the slots see them from the next coffee_analysis_step on.  *accepted = how many fit
+ * (submitted minus drained never exceeds query_capacity).  A query with num_moves outside 0..x*y, a move >= 4*x*y or max_visits
+ * outside 0..node_cap-4 fails the call with COFFEE_EINVAL and submits nothing. */
+int coffee_analysis_submit(coffee_analysis* h, const coffee_analysis_query* queries, int n, int* accepted);
+/* The checks of coffee_analysis_submit that need only the geometry (no engine, no device). */
+int coffee_analysis_query_check(int x, int y, int win_len, const coffee_analysis_query* q);
+/* Copies up to max finished results, in completion order, to host arrays: header_out [max],
+ * moves_out [max][4*x*y] (records past num_children zeroed; NULL = headers only) and frees
+ * their capacity.  Synchronises the engine stream. */
+int coffee_analysis_drain(coffee_analysis* h, int max, coffee_analysis_result* header_out,
+                          coffee_analysis_move* moves_out, int* n_out);
+int coffee_analysis_stats_get(coffee_analysis* h, coffee_analysis_stats* out);
+/* The self-play inspectors' layouts (coffee_selfplay_game_info / _game_tree / _root_policy). */
+int coffee_analysis_game_info(coffee_analysis* h, int slot, int64_t* info);
+int coffee_analysis_game_tree(coffee_analysis* h, int slot, int max_nodes, uint32_t* nodes, uint32_t* edges,
+                              int* n_nodes);
+int coffee_analysis_root_policy(coffee_analysis* h, int slot, float* out);
+
 /* Writes n rows (HOST arrays, drain_rows layout) as a training .npz in the reference's
  * format (TrainingWriteBuffers::writeToZipFile trainingwrite.cpp:566-587): members
  * binaryInputNCHWPacked, globalInputNC, policyTargetsNCMove, globalTargetsNC,

@@ -124,6 +124,50 @@ class MatchStats(ctypes.Structure):
                 ("nn_audit_switches", ctypes.c_uint64 * 2), ("nn_audit_max_diff", ctypes.c_double * 2)]
 
 
+ANALYSIS_MAX_MOVES = 100
+ANALYSIS_MAX_PV = 16
+ANALYSIS_OK, ANALYSIS_ILLEGAL_MOVE, ANALYSIS_GAME_OVER, ANALYSIS_NO_LEGAL_MOVE = 0, 1, 2, 3
+
+
+class AnalysisConfig(ctypes.Structure):
+    _fields_ = [
+        ("x", ctypes.c_int32), ("y", ctypes.c_int32), ("win_len", ctypes.c_int32),
+        ("num_slots", ctypes.c_int32), ("node_cap", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
+        ("model_path", ctypes.c_char_p),
+        ("search", SearchParams),
+        ("nn_cache_log2", ctypes.c_int32),
+        ("nn_batch_cap", ctypes.c_int32),
+        ("nn_precision", ctypes.c_int32),
+        ("engines_per_device", ctypes.c_int32),
+        ("commit_interval", ctypes.c_int32),
+        ("query_capacity", ctypes.c_int32),
+        ("max_pv_len", ctypes.c_int32),
+    ]
+
+
+class AnalysisStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ["rounds", "playouts", "nn_evals", "queries_loaded", "queries_finished", "queries_rejected", "errors",
+                 "nn_precision", "nn_audits", "nn_audit_switches"]] + [("nn_audit_max_diff", ctypes.c_double)]
+
+
+# coffee_analysis_query / _result / _move as numpy record layouts (C alignment)
+ANALYSIS_QUERY = np.dtype([("id", np.uint64), ("rng_counter", np.uint64), ("stream", np.uint32),
+                           ("game_num", np.uint32), ("num_moves", np.int32), ("max_visits", np.int32),
+                           ("moves", np.uint16, (ANALYSIS_MAX_MOVES,))], align=True)
+ANALYSIS_RESULT = np.dtype([("id", np.uint64), ("status", np.int32), ("info", np.int32), ("turn", np.int32),
+                            ("pla", np.int32), ("visits", np.uint32), ("weight_sum", np.float32),
+                            ("utility_avg", np.float32), ("win_loss_avg", np.float32), ("nn_win", np.float32),
+                            ("nn_loss", np.float32), ("num_children", np.int32), ("pad", np.int32)], align=True)
+ANALYSIS_MOVE = np.dtype([("move", np.int32), ("edge_visits", np.uint32), ("visits", np.uint32),
+                          ("weight_sum", np.float32), ("utility_avg", np.float32), ("win_loss_avg", np.float32),
+                          ("prior", np.float32), ("lcb", np.float32), ("radius", np.float32),
+                          ("play_selection_value", np.float32), ("order", np.int32), ("pv_len", np.int32),
+                          ("pv", np.uint16, (ANALYSIS_MAX_PV,))], align=True)
+assert ANALYSIS_QUERY.itemsize == 232 and ANALYSIS_RESULT.itemsize == 56 and ANALYSIS_MOVE.itemsize == 80
+
+
 # Every symbol include/katacoffee.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "coffee_last_error", "coffee_abi_version", "coffee_device_count", "coffee_set_device", "coffee_device_compute_units", "coffee_malloc",
@@ -141,6 +185,10 @@ EXPORTS = [
     "coffee_match_params_default", "coffee_match_create", "coffee_match_step", "coffee_match_sync",
     "coffee_match_stream", "coffee_match_destroy", "coffee_match_stats_get", "coffee_match_drain_games",
     "coffee_match_score", "coffee_match_game_info", "coffee_match_game_tree", "coffee_match_root_policy",
+    "coffee_analysis_params_default", "coffee_analysis_create", "coffee_analysis_step", "coffee_analysis_sync",
+    "coffee_analysis_stream", "coffee_analysis_destroy", "coffee_analysis_submit", "coffee_analysis_query_check",
+    "coffee_analysis_drain", "coffee_analysis_stats_get", "coffee_analysis_game_info", "coffee_analysis_game_tree",
+    "coffee_analysis_root_policy",
 ]
 
 
@@ -217,6 +265,20 @@ def lib():
         L.coffee_match_game_info.argtypes = [c_p, c_i, c_p]
         L.coffee_match_game_tree.argtypes = [c_p, c_i, c_i, c_p, c_p, c_p]
         L.coffee_match_root_policy.argtypes = [c_p, c_i, c_p]
+        L.coffee_analysis_params_default.argtypes = [c_p]
+        L.coffee_analysis_params_default.restype = None
+        L.coffee_analysis_create.argtypes = [c_p, c_p]
+        L.coffee_analysis_step.argtypes = [c_p, c_i, c_p]
+        L.coffee_analysis_sync.argtypes = [c_p]
+        L.coffee_analysis_stream.argtypes = [c_p, c_p]
+        L.coffee_analysis_destroy.argtypes = [c_p]
+        L.coffee_analysis_submit.argtypes = [c_p, c_p, c_i, c_p]
+        L.coffee_analysis_query_check.argtypes = [c_i, c_i, c_i, c_p]
+        L.coffee_analysis_drain.argtypes = [c_p, c_i, c_p, c_p, c_p]
+        L.coffee_analysis_stats_get.argtypes = [c_p, c_p]
+        L.coffee_analysis_game_info.argtypes = [c_p, c_i, c_p]
+        L.coffee_analysis_game_tree.argtypes = [c_p, c_i, c_i, c_p, c_p, c_p]
+        L.coffee_analysis_root_policy.argtypes = [c_p, c_i, c_p]
         _lib = L
     return _lib
 
@@ -246,6 +308,50 @@ def default_match_params(**over):
     for k, v in over.items():
         setattr(p, k, v)
     return p
+
+
+def default_analysis_params(**over):
+    """coffee_analysis_params_default: the match values with analysis_example.cfg's visits, LCB
+    settings and root symmetries; root noise off and no pruning of the reported values."""
+    p = SearchParams()
+    lib().coffee_analysis_params_default(ctypes.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def analysis_queries(queries):
+    """Queries as an ANALYSIS_QUERY array.  queries: such an array, or a list of dicts with
+    `id`, `moves` (policy positions dir * A + cell from the empty board) and optionally
+    `max_visits` (0 = the config's), `stream` (default: the low 32 bits of id), `game_num` (0)
+    and `rng_counter` (0)."""
+    if isinstance(queries, np.ndarray):
+        if queries.dtype != ANALYSIS_QUERY:
+            raise CoffeeError("queries: a structured array must have dtype ANALYSIS_QUERY")
+        return np.ascontiguousarray(queries)
+    out = np.zeros(len(queries), ANALYSIS_QUERY)
+    for i, q in enumerate(queries):
+        moves = list(q.get("moves", ()))
+        if len(moves) > ANALYSIS_MAX_MOVES:
+            raise CoffeeError("query %r: more than %d moves" % (q.get("id"), ANALYSIS_MAX_MOVES))
+        if any(not 0 <= int(m) < 65536 for m in moves):
+            raise CoffeeError("query %r: a move is out of range" % (q.get("id"),))
+        out[i]["id"] = q["id"]
+        out[i]["stream"] = q.get("stream", int(q["id"]) & 0xFFFFFFFF)
+        out[i]["game_num"] = q.get("game_num", 0)
+        out[i]["rng_counter"] = q.get("rng_counter", 0)
+        out[i]["max_visits"] = q.get("max_visits", 0)
+        out[i]["num_moves"] = len(moves)
+        out[i]["moves"][:len(moves)] = moves
+    return out
+
+
+def analysis_query_check(X, Y, W, query):
+    """The host-side checks of a submit (coffee_analysis_query_check): raises CoffeeError naming
+    the field.  Needs no device."""
+    q = analysis_queries([query] if isinstance(query, dict) else query)
+    for i in range(len(q)):
+        check(lib().coffee_analysis_query_check(X, Y, W, ctypes.c_void_p(q[i:i + 1].ctypes.data)))
 
 
 def match_score(header):
@@ -703,6 +809,133 @@ class Match:
     def close(self):
         if self.h:
             lib().coffee_match_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Analysis:
+    """One device's batched position analysis (coffee_analysis_*): num_slots concurrent
+    searches of queued positions.  submit() queues queries (see analysis_queries), step() runs
+    rounds, drain() returns the finished results as structured arrays: headers [n]
+    (ANALYSIS_RESULT) and per-child records [n][P] (ANALYSIS_MOVE, child-slot order, the first
+    num_children valid).  Values are from white's perspective as stored; `pla` is the side to
+    move.  search: a SearchParams to start from instead of default_analysis_params(); keyword
+    overrides apply on top of either."""
+
+    def __init__(self, X=5, Y=5, W=4, num_slots=64, model_path=None, search=None, seed=1, node_cap=0,
+                 commit_interval=0, nn_cache_log2=0, nn_batch_cap=0, nn_precision="default", engines_per_device=0,
+                 query_capacity=0, max_pv_len=ANALYSIS_MAX_PV, **search_over):
+        self.X, self.Y, self.W = X, Y, W
+        self.A, self.P = X * Y, 4 * X * Y
+        self.num_slots = num_slots
+        search = default_analysis_params() if search is None else SearchParams.from_buffer_copy(search)
+        for k, v in search_over.items():
+            setattr(search, k, v)
+        cfg = AnalysisConfig()
+        cfg.x, cfg.y, cfg.win_len = X, Y, W
+        cfg.num_slots = num_slots
+        cfg.node_cap = node_cap
+        cfg.seed = seed
+        self._model = model_path.encode() if model_path else None
+        cfg.model_path = self._model
+        cfg.search = search
+        cfg.nn_cache_log2 = nn_cache_log2
+        cfg.nn_batch_cap = nn_batch_cap
+        cfg.nn_precision = PRECISIONS[nn_precision]
+        cfg.engines_per_device = engines_per_device
+        cfg.commit_interval = commit_interval
+        cfg.query_capacity = query_capacity if query_capacity else 4 * num_slots
+        cfg.max_pv_len = max_pv_len
+        self.query_capacity = cfg.query_capacity
+        self.cfg = cfg
+        self.h = ctypes.c_void_p()
+        check(lib().coffee_analysis_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+
+    def submit(self, queries):
+        """Queues queries; returns how many were accepted (the first ones): submitted minus
+        drained never exceeds query_capacity."""
+        q = analysis_queries(queries)
+        n = ctypes.c_int()
+        check(lib().coffee_analysis_submit(self.h, _ptr(q), len(q), ctypes.byref(n)))
+        return n.value
+
+    def step(self, rounds, stream=None):
+        check(lib().coffee_analysis_step(self.h, rounds, stream))
+
+    def sync(self):
+        check(lib().coffee_analysis_sync(self.h))
+
+    def drain(self, max_results=None):
+        """(headers [n], moves [n][P]) of the finished results, in completion order."""
+        cap = self.query_capacity if max_results is None else min(max_results, self.query_capacity)
+        header = np.zeros(cap, ANALYSIS_RESULT)
+        moves = np.zeros((cap, self.P), ANALYSIS_MOVE)
+        n = ctypes.c_int()
+        check(lib().coffee_analysis_drain(self.h, cap, _ptr(header), _ptr(moves), ctypes.byref(n)))
+        return header[:n.value], moves[:n.value]
+
+    def analyze(self, queries, rounds_per_step=32, max_steps=1 << 20):
+        """Submits every query (as capacity allows), steps and drains until each id is back;
+        returns (headers, moves) in the order of `queries`.  The ids must be distinct."""
+        q = analysis_queries(queries)
+        ids = [int(i) for i in q["id"]]
+        if len(set(ids)) != len(ids):
+            raise CoffeeError("analyze: query ids must be distinct")
+        sent, got = 0, {}
+        for _ in range(max_steps):
+            if len(got) == len(ids):
+                break
+            if sent < len(q):
+                sent += self.submit(q[sent:])
+            self.step(rounds_per_step)
+            h, m = self.drain()
+            for i in range(len(h)):
+                got[int(h[i]["id"])] = (h[i].copy(), m[i].copy())
+        else:
+            raise CoffeeError("analyze: the queries did not finish")
+        header = np.zeros(len(ids), ANALYSIS_RESULT)
+        moves = np.zeros((len(ids), self.P), ANALYSIS_MOVE)
+        for k, i in enumerate(ids):
+            header[k], moves[k] = got[i]
+        return header, moves
+
+    def stats(self):
+        s = AnalysisStats()
+        check(lib().coffee_analysis_stats_get(self.h, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in AnalysisStats._fields_}
+
+    def stream_ptr(self):
+        p = ctypes.c_void_p()
+        check(lib().coffee_analysis_stream(self.h, ctypes.byref(p)))
+        return p.value
+
+    def game_info(self, slot):
+        info = np.zeros(16, np.int64)
+        check(lib().coffee_analysis_game_info(self.h, slot, _ptr(info)))
+        keys = ["phase", "rootK", "liveCount", "rootIdx", "gameNum", "turn", "pla", "finished", "winner",
+                "playouts", "nnEvals", "moves", "gamesFinished", "lastCell", "lastDir", "rngCtr"]
+        return dict(zip(keys, info.tolist()))
+
+    def game_tree(self, slot, max_nodes=4096):
+        nodes = np.zeros((max_nodes, 24), np.uint32)
+        edges = np.zeros((max_nodes, self.P, 3), np.uint32)
+        n = ctypes.c_int()
+        check(lib().coffee_analysis_game_tree(self.h, slot, max_nodes, _ptr(nodes), _ptr(edges), ctypes.byref(n)))
+        return nodes[:n.value], edges[:n.value]
+
+    def root_policy(self, slot):
+        out = np.zeros(self.P, np.float32)
+        check(lib().coffee_analysis_root_policy(self.h, slot, _ptr(out)))
+        return out
+
+    def close(self):
+        if self.h:
+            lib().coffee_analysis_destroy(self.h)
             self.h = ctypes.c_void_p()
 
     def __del__(self):

@@ -565,6 +565,128 @@ int coffee_match_root_policy(coffee_match* h, int slot, float* out) {
   });
 }
 
+// ---- batched position analysis: the self-play engine in analysis mode ----
+
+void coffee_analysis_params_default(coffee_search_params* p) {
+  if(!p)
+    return;
+  coffee_match_params_default(p);
+  // cpp/configs/analysis_example.cfg:66, :278-285 (the commented values are the defaults)
+  p->max_visits = 500;
+  p->use_lcb_for_selection = 1;
+  p->lcb_stdevs = 5.0f;
+  p->min_visit_prop_for_lcb = 0.15f;
+  p->root_num_symmetries_to_sample = 1;
+  p->root_noise_enabled = 0;
+  // the reported play-selection values are unpruned
+  p->chosen_move_subtract = 0.0f;
+  p->chosen_move_prune = 0.0f;
+}
+
+struct coffee_analysis {
+  SelfplayEngine* eng;
+};
+
+int coffee_analysis_create(const coffee_analysis_config* cfg, coffee_analysis** out) {
+  return guarded([&] {
+    need(cfg && out, "NULL argument");
+    coffee_analysis* h = new coffee_analysis{nullptr};
+    try {
+      h->eng = new SelfplayEngine(*cfg);  // validates the config before its first HIP call
+    } catch(...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+  });
+}
+
+int coffee_analysis_step(coffee_analysis* h, int rounds, void* stream) {
+  return guarded([&] {
+    need(h && h->eng, "NULL handle");
+    need(rounds >= 0, "rounds must be >= 0");
+    h->eng->step(rounds, (hipStream_t)stream);
+  });
+}
+
+int coffee_analysis_sync(coffee_analysis* h) {
+  return guarded([&] {
+    need(h && h->eng, "NULL handle");
+    h->eng->sync();
+  });
+}
+
+int coffee_analysis_stream(coffee_analysis* h, void** stream) {
+  return guarded([&] {
+    need(h && h->eng && stream, "NULL argument");
+    *stream = (void*)h->eng->stream();
+  });
+}
+
+int coffee_analysis_destroy(coffee_analysis* h) {
+  return guarded([&] {
+    if(h) {
+      delete h->eng;
+      delete h;
+    }
+  });
+}
+
+int coffee_analysis_query_check(int x, int y, int win_len, const coffee_analysis_query* q) {
+  return guarded([&] {
+    need(q != nullptr, "NULL argument");
+    checkGeom(x, y, win_len);
+    validateAnalysisQuery(x, y, *q);
+  });
+}
+
+int coffee_analysis_submit(coffee_analysis* h, const coffee_analysis_query* queries, int n, int* accepted) {
+  return guarded([&] {
+    need(h && h->eng && accepted, "NULL argument");
+    need(n >= 0 && (n == 0 || queries), "n must be >= 0 and queries non-NULL");
+    *accepted = 0;
+    *accepted = h->eng->analysisSubmit(queries, n);
+  });
+}
+
+int coffee_analysis_drain(coffee_analysis* h, int max, coffee_analysis_result* header_out,
+                          coffee_analysis_move* moves_out, int* n_out) {
+  return guarded([&] {
+    need(h && h->eng && n_out, "NULL argument");
+    need(max >= 0, "max must be >= 0");
+    *n_out = h->eng->analysisDrain(max, header_out, moves_out);
+  });
+}
+
+int coffee_analysis_stats_get(coffee_analysis* h, coffee_analysis_stats* out) {
+  return guarded([&] {
+    need(h && h->eng && out, "NULL argument");
+    h->eng->analysisStats(*out);
+  });
+}
+
+int coffee_analysis_game_info(coffee_analysis* h, int slot, int64_t* info) {
+  return guarded([&] {
+    need(h && h->eng && info, "NULL argument");
+    h->eng->gameInfo(slot, info);
+  });
+}
+
+int coffee_analysis_game_tree(coffee_analysis* h, int slot, int max_nodes, uint32_t* nodes, uint32_t* edges,
+                              int* n_nodes) {
+  return guarded([&] {
+    need(h && h->eng && n_nodes, "NULL argument");
+    *n_nodes = h->eng->gameTree(slot, max_nodes, nodes, edges);
+  });
+}
+
+int coffee_analysis_root_policy(coffee_analysis* h, int slot, float* out) {
+  return guarded([&] {
+    need(h && h->eng && out, "NULL argument");
+    h->eng->rootPolicy(slot, out);
+  });
+}
+
 int coffee_write_npz(const char* path, int n, int x, int y, const uint8_t* bin, const float* glob,
                      const int16_t* pol, const float* gtgt, const int8_t* value) {
   return guarded([&] {

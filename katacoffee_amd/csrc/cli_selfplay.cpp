@@ -296,12 +296,19 @@ static void runGpu(int gpu, int server, int perGpu, int slot, int share, const S
 #ifdef KATAGO_GATEKEEPER
 int gatekeeperMain(int argc, char** argv);  // cli_gatekeeper.cpp
 #endif
+#ifdef KATAGO_ANALYSIS
+int analysisMain(int argc, char** argv);  // cli_analysis.cpp
+#endif
 
 int main(int argc, char** argv) {
 #ifdef KATAGO_GATEKEEPER
   // (a build of this file alone -- the sanitizer harness -- has the selfplay command only)
   if(argc >= 2 && std::string(argv[1]) == "gatekeeper")
     return gatekeeperMain(argc, argv);
+#endif
+#ifdef KATAGO_ANALYSIS
+  if(argc >= 2 && std::string(argv[1]) == "analysis")
+    return analysisMain(argc, argv);
 #endif
   if(argc < 2 || std::string(argv[1]) != "selfplay")
     die("usage: katago selfplay -config <cfg> -models-dir <dir> -output-dir <dir> [-max-games-total N] "

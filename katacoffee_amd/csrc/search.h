@@ -17,9 +17,11 @@
 //   float     accPolicy/rawPolicy/rootNoised[G][P]     root symmetry accumulation / noised prior
 //   int32     pathNode/pathSlot[G][MAX_DEPTH]          the current playout's path
 //   TurnRec   turns[G][maxTurns], int16 turnPol[G][maxTurns][P]  per-move records for rows
+// Position analysis (DESIGN.md "Analysis") adds a query ring, a result ring and a per-slot record.
 // Node indices are an allocator detail: results depend only on child-slot order,
 // which is the reference's expansion order.
 #pragma once
+#include "../../include/katacoffee.h"
 #include "kc_common.h"
 
 namespace kc {
@@ -200,6 +202,16 @@ struct FinRec {
   int32_t pad;
 };
 
+// Analysis: the query a slot holds (busy 0: the slot is idle).
+struct AnalysisSlot {
+  uint64_t id;
+  int32_t busy, pad;
+};
+// SearchDev::aCtr entries: queries popped from the ring, queries submitted (written by the host
+// on the engine stream, between kernels), results written, and the stats' loaded / finished /
+// rejected counts.
+enum AnalysisCounter { AC_POPPED = 0, AC_SUBMITTED, AC_RESULTS, AC_LOADED, AC_FINISHED, AC_REJECTED, AC_N };
+
 struct GameDev {
   DBoard root;
   DBoard leaf;
@@ -340,6 +352,20 @@ struct SearchDev {
   DPtr<float> cPol1;
   DPtr<float> cVal1;
   DPtr<uint32_t> cTag1;
+  // position analysis (DESIGN.md "Analysis"): a slot holds one query or is idle (phase PH_COMMIT
+  // without a commit-list entry, which the round kernels skip).  Queries wait in aQuery, a ring
+  // of aCap entries the host fills; kAnalysisLoad / kAnalysisReport pop them and write results
+  // into the rings aRes / aMoves.  Outstanding queries never exceed aCap (host), so neither ring
+  // overflows.
+  int32_t analysisMode;
+  int32_t aCap;
+  int32_t aMaxPv;             // principal-variation moves reported per child (<= COFFEE_ANALYSIS_MAX_PV)
+  DPtr<coffee_analysis_query> aQuery;   // [aCap]
+  DPtr<coffee_analysis_result> aRes;    // [aCap]
+  DPtr<coffee_analysis_move> aMoves;    // [aCap][P]
+  DPtr<unsigned long long> aCtr;        // [AC_N] running counts (AnalysisCounter)
+  DPtr<AnalysisSlot> aSlot;             // [G]
+  unsigned long long aSubmitted;        // host copy only: queries submitted so far (launchCommit hands it on)
 };
 
 // Match play: the candidate (net 1) plays black (player 1) in game number n of global
@@ -377,6 +403,8 @@ void launchBackupSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st,
                         hipEvent_t e1 = nullptr);
 void launchResolve(const SearchDev& d, const SearchDev* dd, hipStream_t st);
 void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st);  // + kRows
+// (d.analysisMode: launchSelfplayInit leaves every slot idle, and launchCommit passes d.aSubmitted
+// to the device, reports the listed searches and lets the idle slots pop queued queries)
 void launchGameTree(const SearchDev* dd, int slot, int maxNodes, uint32_t* nodesOut, uint32_t* edgesOut,
                     int32_t* count, hipStream_t st);
 // Dynamic LDS bytes the commit kernel needs for node_cap `cap`.

@@ -3973,6 +3973,305 @@ __global__ void kGameTree(const SearchDev* __restrict__ dp, int g, int maxNodes,
 }
 
 // ---------------------------------------------------------------------------
+// Position analysis (DESIGN.md "Analysis").  A slot holds one query or is idle.  An idle slot
+// stands in PH_COMMIT with no leaf and no commit-list entry: kSelect gives it no network row
+// and kBackup returns at once, so the round kernels run unchanged.  A search that reaches its
+// visit limit is listed for the commit like a self-play move; kAnalysisReport takes kCommit's
+// place, writes the result and refills the slot from the query ring.
+
+// The next queued query's ring entry, or -1 (uniform).  The submitted count is written by the
+// host between kernels only.
+KC_D int popQuery(const SearchDev& d, int lane) {
+  int q = -1;
+  if(lane == 0) {
+    unsigned long long* c = d.aCtr;
+    const unsigned long long sub = c[AC_SUBMITTED];
+    unsigned long long h = atomicAdd(&c[AC_POPPED], 0ull);
+    while(h < sub) {
+      const unsigned long long prev = atomicCAS(&c[AC_POPPED], h, h + 1ull);
+      if(prev == h) {
+        q = (int)(h % (unsigned long long)d.aCap);
+        break;
+      }
+      h = prev;
+    }
+  }
+  return bcastLane(q, 0);
+}
+
+// The ring entry of the next result (uniform).  Results outstanding never exceed aCap: every
+// result answers a submitted query, and the host submits no more than aCap undrained ones.
+KC_D int newResult(const SearchDev& d, int lane) {
+  int r = 0;
+  if(lane == 0)
+    r = (int)(atomicAdd(&d.aCtr[AC_RESULTS], 1ull) % (unsigned long long)d.aCap);
+  return bcastLane(r, 0);
+}
+
+// Gives the slot the next queued query, or leaves it idle.  A query's moves are replayed from
+// the empty board with the device rules, each checked before it is played; an illegal move, a
+// move list that ends the game and a position without a legal move are answered at once (no
+// search, GameDev::err untouched) and the next query is tried.  Otherwise the slot starts a
+// fresh search the way startForkGame starts a forked game: stream seeded by startGame's
+// formula from (seed, stream, game_num), game hashes from its first two draws, cleared tables,
+// the replayed moves as unsearched turn records.  s: the slot's LDS copy (stored by the caller).
+template <bool W1>
+KC_D void analysisRefill(const GV& v, GameDev& s) {
+  const SearchDev& d = v.d;
+  const int A = d.A, P = d.P;
+  for(;;) {
+    const int qi = popQuery(d, v.lane);
+    if(qi < 0) {
+      s.phase = PH_COMMIT;
+      s.leafKind = LEAF_NONE;
+      if(v.lane == 0)
+        d.aSlot[v.g].busy = 0;
+      return;
+    }
+    const coffee_analysis_query* q = d.aQuery + qi;
+    const uint64_t id = q->id;
+    // the host checked both ranges (coffee_analysis_submit); nothing here indexes past them anyway
+    // every decision of the replay is taken on scalar values (each lane computes the same ones,
+    // which the compiler cannot know): the branches stay scalar and every lane stays active
+    // for the wave-wide rules (playMoveWave's ballot)
+    const int nm = __builtin_amdgcn_readfirstlane(min(max((int)q->num_moves, 0), min(A, COFFEE_ANALYSIS_MAX_MOVES)));
+    boardInit(v.T, s.root);
+    waveSync();
+    int bad = -1;
+    for(int t = 0; t < nm; t++) {
+      const int mv = __builtin_amdgcn_readfirstlane((int)q->moves[t]);
+      bool ok = __builtin_amdgcn_readfirstlane(s.root.finished) == 0 && mv < P;
+      if(ok)
+        ok = __builtin_amdgcn_readfirstlane((int)isLegal<W1>(v.T, s.root, mv % A, mv / A)) != 0;
+      if(!ok) {
+        bad = t;
+        break;
+      }
+      playMoveWave<W1>(v.T, s.root, mv % A, mv / A);
+      waveSync();
+    }
+    const int over = __builtin_amdgcn_readfirstlane(s.root.finished);
+    if(bad >= 0 || over != 0) {
+      const int ri = newResult(d, v.lane);
+      if(v.lane == 0) {
+        coffee_analysis_result r;
+        memset(&r, 0, sizeof(r));
+        r.id = id;
+        if(bad >= 0) {
+          r.status = COFFEE_ANALYSIS_ILLEGAL_MOVE;
+          r.info = bad;
+        } else if(s.root.winner == 0 && s.root.turn < A) {
+          r.status = COFFEE_ANALYSIS_NO_LEGAL_MOVE;
+        } else {
+          r.status = COFFEE_ANALYSIS_GAME_OVER;
+          r.info = s.root.winner;
+        }
+        r.turn = s.root.turn;
+        r.pla = s.root.pla;
+        d.aRes[ri] = r;
+        atomicAdd(&d.aCtr[AC_LOADED], 1ull);
+        atomicAdd(&d.aCtr[AC_FINISHED], 1ull);
+        atomicAdd(&d.aCtr[AC_REJECTED], 1ull);
+      }
+      continue;
+    }
+    s.rngSeed = mix64(d.seed ^ mix64(((uint64_t)q->stream << 32) | (uint32_t)q->game_num));
+    s.gameNum = (int32_t)q->game_num;
+    s.startGen = *d.modelGen;
+    clearTables(v, s);
+    TurnRec* tr = v.turns();
+    for(int t = v.lane; t < nm; t += 64) {
+      const int mv = (int)q->moves[t];
+      TurnRec rec;
+      memset(&rec, 0, sizeof(rec));
+      rec.gen = (uint8_t)*d.modelGen;
+      rec.cell = (int8_t)(mv % A);
+      rec.dir = (int8_t)(mv / A);
+      tr[t] = rec;
+    }
+    s.numTurns = nm;
+    s.startTurn = nm;
+    s.moves = (uint64_t)nm;
+    s.initLeft = 0;
+    s.gameMode = 0;
+    s.sideCount = 0;
+    s.sideNext = 0;
+    s.sideMode = 0;
+    s.startDelay = 0;
+    DRng rng{s.rngSeed, 0};
+    s.gameHash0 = rng.next();
+    s.gameHash1 = rng.next();
+    const uint64_t ctr = q->rng_counter;
+    s.rngCtr = ctr != 0 ? ctr : rng.ctr;
+    const int mvis = (int)q->max_visits;
+    s.visitLimit = min(mvis > 0 ? mvis : d.sp.maxVisits, d.cap - 4);
+    s.moveWeight = 1.0f;
+    s.noNoise = 0;
+    s.phase = PH_ROOTEVAL;
+    s.rootK = 0;
+    s.leafKind = LEAF_NONE;
+    if(v.lane == 0) {
+      d.aSlot[v.g].id = id;
+      d.aSlot[v.g].busy = 1;
+      atomicAdd(&d.aCtr[AC_LOADED], 1ull);
+    }
+    waveSync();
+    return;
+  }
+}
+
+// Every slot idle (after kInit started a game in each).
+__global__ void kAnalysisInit(const SearchDev* __restrict__ dp) {
+  const SearchDev& d = *dp;
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if(g >= d.G)
+    return;
+  d.games[g].phase = PH_COMMIT;
+  d.games[g].leafKind = LEAF_NONE;
+  d.aSlot[g].busy = 0;
+}
+
+__global__ void kAnalysisSubmitted(const SearchDev* __restrict__ dp, unsigned long long submitted) {
+  dp->aCtr[AC_SUBMITTED] = submitted;
+}
+
+// One wave per slot: an idle slot takes the next queued query (launched with every report,
+// and by every step before its first round, after the host's submissions).
+template <int NI>
+__global__ void __launch_bounds__(64) kAnalysisLoad(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp) {
+  // (constant views, as in kBackup: uniform reads stay scalar loads after the kernel's own stores)
+  const SearchDev& d = *uniformConst(dp);
+  const DTables& T = *uniformConst(Tp);
+  const int g = blockIdx.x;
+  if(g >= d.G || d.aSlot[g].busy != 0)
+    return;
+  if(d.aCtr[AC_POPPED] >= d.aCtr[AC_SUBMITTED])  // nothing queued (a later pop re-checks atomically)
+    return;
+  __shared__ GameDev s;
+  GV v(d, T, g);
+  loadGame(v, s);
+  analysisRefill<W1_OF<NI>>(v, s);
+  waveSync();
+  storeGame(v, s);
+}
+
+// One wave per finished search, over the commit list (where self-play runs kCommit): the
+// result header from the root's record, one record per root child in child-slot order -- lane
+// l holds children l, l + 64, ... as everywhere -- and the slot's refill.  Per child: the
+// edge and the child's record as stored (white's perspective), the root's NN policy of the
+// move before temperature and noise, lcbAndRadius, the play-selection value at the settings
+// the move choice uses (no pruning when chosen_move_subtract / _prune are 0), its rank, and
+// the principal variation: each lane walks its own children's lines, at every node to the
+// child with the most edge visits (ties: lower slot), until a node without children or a
+// terminal node.  The tree is not changed.
+template <int NI>
+__global__ void __launch_bounds__(64) kAnalysisReport(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp) {
+  // (constant views, as in kBackup: uniform reads stay scalar loads after the kernel's own stores)
+  const SearchDev& d = *uniformConst(dp);
+  const DTables& T = *uniformConst(Tp);
+  if((int)blockIdx.x >= *d.commitCount)
+    return;
+  const int g = d.commitList[blockIdx.x];
+  __shared__ int posv[MAX_P];
+  __shared__ float vals[MAX_P];
+  __shared__ GameDev s;
+  // a list entry is reported once: the list outlives its commit until the next kSelect
+  // empties it, and the launch also runs at the start of a step
+  if(d.aSlot[g].busy == 0 || d.games[g].phase != PH_COMMIT)
+    return;
+  GV v(d, T, g);
+  loadGame(v, s);
+  const SP& sp = d.sp;
+  const Node* NS = v.nodes();
+  const Node root = NS[s.rootIdx];
+  const int k = root.numChildren, pla = root.nextPla;
+  // (a root without children gets the direct policy moves here: not children, not reported)
+  playSelectionValues<NI>(v, sp, s, 0.0f, true, posv, vals, sp.useLcb != 0);
+  const int ri = newResult(d, v.lane);
+  const NodeEdges E = v.edges(s.rootIdx, root.edgeBase);
+  const float* rp = v.pol(s.rootIdx);
+  const Edge* pool = v.edgePool();
+  const int maxPv = min(d.aMaxPv, COFFEE_ANALYSIS_MAX_PV);
+  coffee_analysis_move* out = d.aMoves + (size_t)ri * d.P;
+#pragma unroll
+  for(int j = 0; j < NI; j++) {
+    const int i = v.lane + 64 * j;
+    if(i >= k)
+      continue;
+    const Edge e = E[i];
+    const Node c = NS[e.child];
+    coffee_analysis_move* m = out + i;
+    m->move = (int32_t)e.move;
+    m->edge_visits = e.visits;
+    m->visits = c.visits;
+    m->weight_sum = c.weightSum;
+    m->utility_avg = c.utilityAvg;
+    m->win_loss_avg = c.winLossAvg;
+    m->prior = rp[e.move];
+    float lcb, radius;
+    lcbAndRadius(sp, pla, c.visits, c.weightSum, c.weightSqSum, c.utilityAvg, c.utilitySqAvg, e.visits, lcb, radius);
+    m->lcb = lcb;
+    m->radius = radius;
+    const float val = vals[i];
+    m->play_selection_value = val;
+    int order = 0;
+    for(int o = 0; o < k; o++) {
+      const float ov = vals[o];
+      order += (ov > val || (ov == val && o < i)) ? 1 : 0;
+    }
+    m->order = order;
+    int len = 0;
+    uint32_t node = e.child;
+    uint32_t mv = e.move;
+    while(len < maxPv) {
+      m->pv[len++] = (uint16_t)mv;
+      const Node& n = NS[node];
+      const int nk = n.numChildren;
+      if(nk == 0 || (n.flags & 2))
+        break;
+      const Edge* inl = v.inlineEdges((int)node);
+      const Edge* pl = pool + n.edgeBase;
+      uint32_t bestVis = 0, bestChild = 0, bestMove = 0;
+      for(int o = 0; o < nk; o++) {
+        const Edge ce = o < INLINE_EDGES ? inl[o] : pl[o - INLINE_EDGES];
+        if(o == 0 || ce.visits > bestVis) {
+          bestVis = ce.visits;
+          bestChild = ce.child;
+          bestMove = ce.move;
+        }
+      }
+      node = bestChild;
+      mv = bestMove;
+    }
+    m->pv_len = len;
+    for(int t = len; t < COFFEE_ANALYSIS_MAX_PV; t++)
+      m->pv[t] = 0;
+  }
+  if(v.lane == 0) {
+    coffee_analysis_result r;
+    r.id = d.aSlot[g].id;
+    r.status = COFFEE_ANALYSIS_OK;
+    r.info = 0;
+    r.turn = s.root.turn;
+    r.pla = s.root.pla;
+    r.visits = root.visits;
+    r.weight_sum = root.weightSum;
+    r.utility_avg = root.utilityAvg;
+    r.win_loss_avg = root.winLossAvg;
+    r.nn_win = root.nnWin;
+    r.nn_loss = root.nnLoss;
+    r.num_children = k;
+    r.pad = 0;
+    d.aRes[ri] = r;
+    atomicAdd(&d.aCtr[AC_FINISHED], 1ull);
+  }
+  waveSync();
+  analysisRefill<W1_OF<NI>>(v, s);
+  waveSync();
+  storeGame(v, s);
+}
+
+// ---------------------------------------------------------------------------
 static int laneItems(int P) { return P <= 128 ? 2 : (P <= 256 ? 4 : 7); }
 
 // ---------------------------------------------------------------------------
@@ -4022,6 +4321,10 @@ void launchStageRows(const SearchDev& d, const SearchDev* dd, uint8_t* dst, unsi
 void launchSelfplayInit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
   hipLaunchKernelGGL(kInit, dim3(d.G), dim3(64), 0, st, dd, d.T);
   KC_HIP(hipGetLastError());
+  if(d.analysisMode) {
+    hipLaunchKernelGGL(kAnalysisInit, dim3((d.G + 255) / 256), dim3(256), 0, st, dd);
+    KC_HIP(hipGetLastError());
+  }
 }
 
 // 256 threads (one wave per SIMD) while each wave keeps at most CP_CH chunks of 64 games: a workgroup
@@ -4115,6 +4418,28 @@ void launchResolve(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
 }
 
 void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
+  if(d.analysisMode) {
+    // nothing is played: the finished searches are reported and their slots refilled, then
+    // the idle slots take the queries submitted so far
+    hipLaunchKernelGGL(kAnalysisSubmitted, dim3(1), dim3(1), 0, st, dd, d.aSubmitted);
+    KC_HIP(hipGetLastError());
+    switch(laneItems(d.P)) {
+      case 2:
+        hipLaunchKernelGGL(kAnalysisReport<2>, dim3(d.G), dim3(64), 0, st, dd, d.T);
+        hipLaunchKernelGGL(kAnalysisLoad<2>, dim3(d.G), dim3(64), 0, st, dd, d.T);
+        break;
+      case 4:
+        hipLaunchKernelGGL(kAnalysisReport<4>, dim3(d.G), dim3(64), 0, st, dd, d.T);
+        hipLaunchKernelGGL(kAnalysisLoad<4>, dim3(d.G), dim3(64), 0, st, dd, d.T);
+        break;
+      default:
+        hipLaunchKernelGGL(kAnalysisReport<7>, dim3(d.G), dim3(64), 0, st, dd, d.T);
+        hipLaunchKernelGGL(kAnalysisLoad<7>, dim3(d.G), dim3(64), 0, st, dd, d.T);
+        break;
+    }
+    KC_HIP(hipGetLastError());
+    return;
+  }
   const size_t lds = commitLdsBytes(d.cap);
   if(d.matchMode) {  // no kRows: match play writes no training rows
     switch(laneItems(d.P)) {

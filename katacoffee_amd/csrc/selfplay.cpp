@@ -148,6 +148,94 @@ coffee_selfplay_config SelfplayEngine::matchBase(const coffee_match_config& c) {
 
 SelfplayEngine::SelfplayEngine(const coffee_match_config& c) : SelfplayEngine(matchBase(c), c.model_path) {}
 
+// The settings analysis rejects: a query is one search from a cleared tree, and nothing is
+// played or recorded, so every setting that keeps a tree, makes rows or plays opening moves
+// has no meaning there.
+void validateAnalysisConfig(const coffee_analysis_config& c) {
+  if(c.x < 2 || c.y < 2 || c.x > MAX_LEN || c.y > MAX_LEN)
+    throw std::invalid_argument("board size must be 2..10 x 2..10");
+  if(c.win_len < 2 || c.win_len > std::max(c.x, c.y))
+    throw std::invalid_argument("win_len must be in 2..max(x, y)");
+  const coffee_search_params& sp = c.search;
+  auto reject = [](bool bad, const char* name, const char* why) {
+    if(bad)
+      throw std::invalid_argument(std::string("analysis: ") + name + " " + why);
+  };
+  const char* keeps = "must be off (every query is searched from a cleared tree)";
+  const char* rows = "must be off (it exists only to make training rows)";
+  reject(sp.cheap_search_prob > 0.0f, "cheap_search_prob", keeps);
+  reject(sp.reduce_visits != 0, "reduce_visits", rows);
+  reject(sp.early_fork_game_prob > 0.0f, "early_fork_game_prob", rows);
+  reject(sp.fork_game_prob > 0.0f, "fork_game_prob", rows);
+  reject(sp.side_position_prob > 0.0f, "side_position_prob", rows);
+  reject(sp.record_tree_positions != 0, "record_tree_positions", rows);
+  reject(sp.policy_surprise_data_weight != 0.0f, "policy_surprise_data_weight", rows);
+  reject(sp.value_surprise_data_weight != 0.0f, "value_surprise_data_weight", rows);
+  reject(sp.init_games_with_policy != 0, "init_games_with_policy", "must be off (a query gives the position)");
+  if(c.num_slots < 1)
+    throw std::invalid_argument("analysis: num_slots must be >= 1");
+  if(c.query_capacity < 1)
+    throw std::invalid_argument("analysis: query_capacity must be >= 1");
+  if(c.max_pv_len < 0 || c.max_pv_len > COFFEE_ANALYSIS_MAX_PV)
+    throw std::invalid_argument("analysis: max_pv_len must be in 0.." + std::to_string(COFFEE_ANALYSIS_MAX_PV));
+}
+
+// the record layouts the Python mirror declares (katacoffee_amd ANALYSIS_*)
+static_assert(sizeof(coffee_analysis_query) == 232 && sizeof(coffee_analysis_result) == 56 &&
+                  sizeof(coffee_analysis_move) == 80,
+              "analysis record layout");
+static_assert(COFFEE_ANALYSIS_MAX_MOVES == MAX_AREA, "a query holds a full board of moves");
+
+void validateAnalysisQuery(int x, int y, const coffee_analysis_query& q) {
+  const int A = x * y, P = 4 * A;
+  if(q.num_moves < 0 || q.num_moves > A || q.num_moves > COFFEE_ANALYSIS_MAX_MOVES)
+    throw std::invalid_argument("analysis query " + std::to_string(q.id) + ": num_moves must be in 0.." +
+                                std::to_string(A));
+  for(int t = 0; t < q.num_moves; t++)
+    if(q.moves[t] >= P)
+      throw std::invalid_argument("analysis query " + std::to_string(q.id) + ": moves[" + std::to_string(t) +
+                                  "] must be < " + std::to_string(P));
+  if(q.max_visits < 0)
+    throw std::invalid_argument("analysis query " + std::to_string(q.id) + ": max_visits must be >= 0");
+}
+
+coffee_selfplay_config SelfplayEngine::analysisBase(const coffee_analysis_config& c) {
+  validateAnalysisConfig(c);  // before the first HIP call
+  coffee_selfplay_config b;
+  memset(&b, 0, sizeof(b));
+  b.x = c.x;
+  b.y = c.y;
+  b.win_len = c.win_len;
+  b.num_games = c.num_slots;
+  b.node_cap = c.node_cap;
+  b.row_capacity = 1;  // never written
+  b.seed = c.seed;
+  b.use_fake_net = c.model_path ? 0 : 1;
+  b.model_path = c.model_path;
+  b.commit_interval = c.commit_interval;
+  b.search = c.search;
+  b.nn_cache_log2 = c.nn_cache_log2;
+  b.nn_batch_cap = c.nn_batch_cap;
+  b.nn_precision = c.nn_precision;
+  b.engines_per_device = c.engines_per_device;
+  return b;
+}
+
+SelfplayEngine::SelfplayEngine(const coffee_analysis_config& c) : SelfplayEngine(analysisBase(c), nullptr) {
+  SearchDev& d = hd_;
+  d.analysisMode = 1;
+  d.aCap = c.query_capacity;
+  d.aMaxPv = c.max_pv_len;
+  d.aQuery = devAlloc<coffee_analysis_query>(owned_, (size_t)d.aCap);
+  d.aRes = devAlloc<coffee_analysis_result>(owned_, (size_t)d.aCap);
+  d.aMoves = devAlloc<coffee_analysis_move>(owned_, (size_t)d.aCap * d.P);
+  d.aCtr = devAlloc<unsigned long long>(owned_, AC_N);
+  d.aSlot = devAlloc<AnalysisSlot>(owned_, (size_t)d.G);
+  KC_HIP(hipMemcpy(dd_, &d, sizeof(SearchDev), hipMemcpyHostToDevice));
+  launchSelfplayInit(d, dd_, stream_);  // again, now in analysis mode: every slot idle
+  KC_HIP(hipStreamSynchronize(stream_));
+}
+
 SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* const* matchPaths) {
   if(c.num_games <= 0)
     throw std::invalid_argument("num_games must be positive");
@@ -431,6 +519,13 @@ void SelfplayEngine::step(int rounds, hipStream_t st) {
   const SearchDev& d = hd_;
   const bool fuse = fuseNow();
   bool selected = false;  // this round's selections ran in the previous round's fused kernel
+  // analysis: the idle slots take the queries submitted since the last step (the report
+  // part of the launch finds nothing new).  Also with rounds == 0: queries that need no
+  // search are then answered without a round
+  if(d.analysisMode) {
+    hd_.aSubmitted = aSubmitted_;
+    launchCommit(d, dd_, st);
+  }
   for(int r = 0; r < rounds; r++) {
     const bool t1 = sampleNow(1);
     // select, network and backup are timed by their own dispatches (kernel start to
@@ -590,6 +685,85 @@ void SelfplayEngine::matchStats(coffee_match_stats& out) {
     out.nn_audit_switches[n] = (uint64_t)nets_[n].auditSwitches;
     out.nn_audit_max_diff[n] = nets_[n].auditSeen;
   }
+}
+
+int SelfplayEngine::analysisSubmit(const coffee_analysis_query* q, int n) {
+  if(!hd_.analysisMode)
+    throw std::invalid_argument("not an analysis engine");
+  for(int i = 0; i < n; i++) {
+    validateAnalysisQuery(xLen_, yLen_, q[i]);
+    if(q[i].max_visits > hd_.cap - 4)
+      throw std::invalid_argument("analysis query " + std::to_string(q[i].id) + ": max_visits must be <= node_cap - 4 (" +
+                                  std::to_string(hd_.cap - 4) + ")");
+  }
+  const uint64_t cap = (uint64_t)hd_.aCap;
+  const int take = (int)std::min<uint64_t>((uint64_t)std::max(n, 0), cap - (aSubmitted_ - aDrained_));
+  // The ring entries [first, first + take) mod cap, in at most two contiguous copies.  They
+  // are free: the queries they held were drained.  The copies return when the data is on the
+  // device and do not wait for the engine stream; kernels learn of the new entries only from
+  // the submitted count, which the next step's first launch carries.
+  const uint64_t first = aSubmitted_ % cap;
+  const uint64_t run0 = std::min<uint64_t>((uint64_t)take, cap - first);
+  if(run0 > 0)
+    KC_HIP(hipMemcpy(hd_.aQuery + first, q, sizeof(coffee_analysis_query) * run0, hipMemcpyHostToDevice));
+  if((uint64_t)take > run0)
+    KC_HIP(hipMemcpy(hd_.aQuery, q + run0, sizeof(coffee_analysis_query) * ((uint64_t)take - run0),
+                     hipMemcpyHostToDevice));
+  aSubmitted_ += (uint64_t)take;
+  return take;
+}
+
+int SelfplayEngine::analysisDrain(int max, coffee_analysis_result* header, coffee_analysis_move* moves) {
+  if(!hd_.analysisMode)
+    throw std::invalid_argument("not an analysis engine");
+  sync();
+  unsigned long long written = 0;
+  KC_HIP(hipMemcpy(&written, hd_.aCtr + AC_RESULTS, 8, hipMemcpyDeviceToHost));
+  const uint64_t cap = (uint64_t)hd_.aCap, P = (uint64_t)hd_.P;
+  const int n = (int)std::min<uint64_t>(written - aDrained_, (uint64_t)std::max(max, 0));
+  if(n > 0 && !header)
+    throw std::invalid_argument("header_out is NULL");
+  const uint64_t first = aDrained_ % cap;
+  const uint64_t run0 = std::min<uint64_t>((uint64_t)n, cap - first), run1 = (uint64_t)n - run0;
+  if(run0 > 0) {
+    KC_HIP(hipMemcpy(header, hd_.aRes + first, sizeof(coffee_analysis_result) * run0, hipMemcpyDeviceToHost));
+    if(moves)
+      KC_HIP(hipMemcpy(moves, hd_.aMoves + first * P, sizeof(coffee_analysis_move) * P * run0, hipMemcpyDeviceToHost));
+  }
+  if(run1 > 0) {
+    KC_HIP(hipMemcpy(header + run0, hd_.aRes, sizeof(coffee_analysis_result) * run1, hipMemcpyDeviceToHost));
+    if(moves)
+      KC_HIP(hipMemcpy(moves + run0 * P, hd_.aMoves, sizeof(coffee_analysis_move) * P * run1, hipMemcpyDeviceToHost));
+  }
+  // a ring entry's records past its children belong to earlier results
+  if(moves)
+    for(int i = 0; i < n; i++) {
+      const uint64_t k = (uint64_t)std::min<int64_t>(std::max<int64_t>(header[i].num_children, 0), (int64_t)P);
+      memset(moves + (uint64_t)i * P + k, 0, sizeof(coffee_analysis_move) * (P - k));
+    }
+  aDrained_ += (uint64_t)n;
+  return n;
+}
+
+void SelfplayEngine::analysisStats(coffee_analysis_stats& out) {
+  if(!hd_.analysisMode)
+    throw std::invalid_argument("not an analysis engine");
+  coffee_selfplay_stats s;
+  stats(s);  // throws on a device error, as for self-play
+  unsigned long long c[AC_N];
+  KC_HIP(hipMemcpy(c, hd_.aCtr, sizeof(c), hipMemcpyDeviceToHost));
+  memset(&out, 0, sizeof(out));
+  out.rounds = s.rounds;
+  out.playouts = s.playouts;
+  out.nn_evals = s.nn_evals;
+  out.queries_loaded = c[AC_LOADED];
+  out.queries_finished = c[AC_FINISHED];
+  out.queries_rejected = c[AC_REJECTED];
+  out.errors = s.errors;
+  out.nn_precision = s.nn_precision;
+  out.nn_audits = s.nn_audits;
+  out.nn_audit_switches = s.nn_audit_switches;
+  out.nn_audit_max_diff = s.nn_audit_max_diff;
 }
 
 int SelfplayEngine::drain(int maxRows, uint8_t* bin, float* glob, int16_t* pol, float* gt, int8_t* val,

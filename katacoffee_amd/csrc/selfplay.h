@@ -16,17 +16,30 @@ SP toSP(const coffee_search_params& p);
 // the offending setting): geometry, and the settings match play rejects because they keep
 // a tree across moves or exist only to make training rows.
 void validateMatchConfig(const coffee_match_config& c);
+// The same for an analysis config: geometry, num_slots, query_capacity, max_pv_len, and the
+// settings of validateMatchConfig plus init_games_with_policy.
+void validateAnalysisConfig(const coffee_analysis_config& c);
+// A query's host-side checks at board x * y (throws std::invalid_argument naming the field):
+// num_moves in 0..x*y, every move < 4*x*y, max_visits >= 0.
+void validateAnalysisQuery(int x, int y, const coffee_analysis_query& q);
 
 class SelfplayEngine {
  public:
   explicit SelfplayEngine(const coffee_selfplay_config& c) : SelfplayEngine(c, nullptr) {}
   // Match mode: net 0 (baseline) against net 1 (candidate); a NULL model path is the stand-in
   explicit SelfplayEngine(const coffee_match_config& c);
+  // Analysis mode (DESIGN.md "Analysis"): the slots search queued positions instead of games
+  explicit SelfplayEngine(const coffee_analysis_config& c);
   ~SelfplayEngine();
   void step(int rounds, hipStream_t st);
   void sync();
   void stats(coffee_selfplay_stats& out);
   void matchStats(coffee_match_stats& out);
+  // Analysis mode: queries into the device ring on the engine stream (returns how many fit),
+  // finished results out of it (returns their number), the counters.
+  int analysisSubmit(const coffee_analysis_query* q, int n);
+  int analysisDrain(int max, coffee_analysis_result* header, coffee_analysis_move* moves);
+  void analysisStats(coffee_analysis_stats& out);
   int drain(int maxRows, uint8_t* bin, float* glob, int16_t* pol, float* gt, int8_t* val, int32_t* meta);
   // header [g][4]; match mode [g][5], the candidate's colour last
   int drainGames(int maxGames, int32_t* header, uint8_t* moves);
@@ -67,6 +80,9 @@ class SelfplayEngine {
   // matchPaths: the two model paths of match mode (self-play: nullptr)
   SelfplayEngine(const coffee_selfplay_config& c, const char* const* matchPaths);
   static coffee_selfplay_config matchBase(const coffee_match_config& c);
+  static coffee_selfplay_config analysisBase(const coffee_analysis_config& c);
+  // analysis: queries submitted / results drained so far
+  uint64_t aSubmitted_ = 0, aDrained_ = 0;
   const DTables* T_ = nullptr;
   // Per-network state: self-play holds one network, match play two (each resolves its
   // precision and runs its audit on its own batches).

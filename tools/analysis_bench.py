@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""Analysis throughput beside self-play at the same settings (DESIGN.md "Analysis").
+
+  python tools/analysis_bench.py [--arch b6c96] [--slots 4096] [--visits 500] [--rounds 2000]
+                                 [--warmup 1000] [--precision default] [--repeats 3]
+
+A kc.Analysis engine is kept fed with queries (random legal openings of 0..8 moves, made with
+the device rules) so that its ring never runs dry; a kc.Selfplay engine with the same net,
+slots, visits, search parameters, commit interval and cache runs the same rounds for
+comparison.  Each figure is taken over `repeats` timed windows of `rounds` rounds after
+`warmup` rounds, host clock around work that ends in a device synchronise; submissions and
+drains happen between the windows' steps and are part of the analysis time, as they are for a
+service.  Prints one JSON line.  The round kernels are the same in both engines, so the
+playouts per second should agree; a gap means idle slots or a refill stall."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import katacoffee_amd as kc  # noqa: E402
+
+X, Y, W, A = 5, 5, 4, 25
+
+
+def openings(n, max_moves, seed):
+    """n random legal move lists of 0..max_moves moves that do not end the game."""
+    rng = np.random.default_rng(seed)
+    cells = np.zeros((n, A), np.uint8)
+    lc, ld = np.full(n, -1, np.int8), np.full(n, 4, np.int8)
+    pla = np.ones(n, np.uint8)
+    want = rng.integers(0, max_moves + 1, n)
+    lists = [[] for _ in range(n)]
+    for t in range(max_moves):
+        on = np.nonzero(want > t)[0]
+        if len(on) == 0:
+            break
+        legal, _ = kc.rules_batch(X, Y, W, cells[on], lc[on], ld[on], pla[on])
+        mv = np.array([rng.choice(np.nonzero(row)[0]) for row in legal], np.int32)
+        oc, fin, _, _, _, _ = kc.play_batch(X, Y, W, cells[on], lc[on], ld[on], pla[on], mv)
+        for j, g in enumerate(on):
+            if fin[j]:
+                want[g] = t  # keep the position before the move that ends the game
+                continue
+            lists[g].append(int(mv[j]))
+            cells[g], lc[g], ld[g], pla[g] = oc[j], mv[j] % A, mv[j] // A, 3 - pla[g]
+    return lists
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--arch", default="b6c96")
+    ap.add_argument("--slots", type=int, default=4096)
+    ap.add_argument("--visits", type=int, default=500)
+    ap.add_argument("--rounds", type=int, default=2000)
+    ap.add_argument("--warmup", type=int, default=1000)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--step", type=int, default=100, help="rounds between submissions and drains")
+    ap.add_argument("--precision", default="default")
+    ap.add_argument("--cache-log2", type=int, default=21)
+    a = ap.parse_args()
+    search = kc.default_analysis_params(max_visits=a.visits)
+    pool = openings(8192, 8, 5)
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, "%s.cfnn" % a.arch)
+        kc.write_random_model(a.arch, 1000, path)
+        common = dict(seed=7, commit_interval=16, nn_cache_log2=a.cache_log2, nn_precision=a.precision)
+        an = kc.Analysis(X, Y, W, num_slots=a.slots, model_path=path, search=search, query_capacity=4 * a.slots,
+                         **common)
+        next_id = [0]
+
+        def feed():
+            free = an.query_capacity - (next_id[0] - feed.drained)
+            qs = [dict(id=next_id[0] + i, moves=pool[(next_id[0] + i) % len(pool)]) for i in range(free)]
+            next_id[0] += an.submit(qs) if qs else 0
+
+        feed.drained = 0
+
+        def run(rounds):
+            done = 0
+            while done < rounds:
+                feed()
+                n = min(a.step, rounds - done)
+                an.step(n)
+                done += n
+                feed.drained += len(an.drain()[0])
+
+        run(a.warmup)
+        an.sync()
+        s0, secs = an.stats(), []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            run(a.rounds)
+            an.sync()
+            secs.append(time.perf_counter() - t0)
+        s1 = an.stats()
+        an.close()
+        t_an = sum(secs)
+        over = {k: getattr(search, k) for k, _ in kc.SearchParams._fields_ if k != "max_visits"}
+        sp = kc.Selfplay(X, Y, W, num_games=a.slots, model_path=path, max_visits=a.visits, start_stagger=a.visits,
+                         **common, **over)
+        sp.step(a.warmup)
+        sp.sync()
+        sp.drain_rows()
+        sp.drain_games()
+        p0, ssecs = sp.stats(), []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            sp.step(a.rounds)
+            sp.sync()
+            ssecs.append(time.perf_counter() - t0)
+            sp.drain_rows()
+            sp.drain_games()
+        p1 = sp.stats()
+        sp.close()
+        t_sp = sum(ssecs)
+    print(json.dumps({
+        "arch": a.arch, "geometry": [X, Y, W], "slots": a.slots, "visits": a.visits, "precision": a.precision,
+        "rounds_per_window": a.rounds, "windows": a.repeats,
+        "analysis": {"positions_per_s": round((s1["queries_finished"] - s0["queries_finished"]) / t_an, 1),
+                     "playouts_per_s": round((s1["playouts"] - s0["playouts"]) / t_an, 0),
+                     "us_per_round": round(1e6 * t_an / (a.rounds * a.repeats), 2),
+                     "window_s": [round(x, 4) for x in secs],
+                     "nn_precision": kc.PRECISION_NAMES.get(s1["nn_precision"], "stand-in")},
+        "selfplay": {"playouts_per_s": round((p1["playouts"] - p0["playouts"]) / t_sp, 0),
+                     "us_per_round": round(1e6 * t_sp / (a.rounds * a.repeats), 2),
+                     "window_s": [round(x, 4) for x in ssecs]},
+    }))
+
+
+if __name__ == "__main__":
+    main()
