@@ -235,7 +235,9 @@ struct NNGeo {
   static constexpr int RING_VH = (32 + 64) * 96 * 4;
   // per-block f32 parameter slabs (double buffered, filled one block ahead)
   static constexpr int NPRM = NN_PRM;
-  static constexpr int OFF_PRM = (OFF_TAB + NTAB * 2 + 15) / 16 * 16;
+  // the boards' batch rows [NB] i32 (read for the input unpack, used again by the output stores)
+  static constexpr int OFF_DST = (OFF_TAB + NTAB * 2 + 3) / 4 * 4;
+  static constexpr int OFF_PRM = (OFF_DST + NB * 4 + 15) / 16 * 16;
   static constexpr int OFF_W = OFF_PRM + 2 * NPRM * 4;
   static constexpr int LDS = OFF_W + RING * WSLOT * 16;
   // the f32 scratch of the g / value branches: in act (dead then), or -- fast borderless,
@@ -263,14 +265,33 @@ __device__ unsigned long long g_nnPhase[4][64];
   do {                                               \
     if(blockIdx.x < 4 && threadIdx.x == 0) {         \
       g_nnPhase[blockIdx.x][(i)] = clock64();        \
-      if((i) == 0 || (i) == 42)                      \
-        g_nnPhase[blockIdx.x][(i) == 0 ? 62 : 63] =  \
+      if((i) == 42)                                  \
+        g_nnPhase[blockIdx.x][63] =                  \
             __builtin_amdgcn_s_memrealtime();        \
     }                                                \
+  } while(0)
+// The entry stamp (slots 0 and 62) is taken at entry and stored once the workgroup is past
+// its early exits: the corrected path's re-evaluation launch, which exits there, would
+// overwrite the real launch's entry stamp.
+#define NN_PHASE_ENTRY()                       \
+  const unsigned long long nnT0 = clock64(),   \
+                           nnR0 = __builtin_amdgcn_s_memrealtime()
+#define NN_PHASE_ENTRY_COMMIT()                \
+  do {                                         \
+    if(blockIdx.x < 4 && threadIdx.x == 0) {   \
+      g_nnPhase[blockIdx.x][0] = nnT0;         \
+      g_nnPhase[blockIdx.x][62] = nnR0;        \
+    }                                          \
   } while(0)
 #else
 #define NN_PHASE(i) \
   do {              \
+  } while(0)
+#define NN_PHASE_ENTRY() \
+  do {                   \
+  } while(0)
+#define NN_PHASE_ENTRY_COMMIT() \
+  do {                          \
   } while(0)
 #endif
 
@@ -722,16 +743,6 @@ KC_D void convTilesB(const uint16_t* __restrict__ act, const h16x8* __restrict__
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
-// Copies a [96][rows] f32 matrix (a [rows][96] linear layer the host stored
-// transposed; global, 16-B aligned) into LDS: consecutive output rows of one wave
-// read consecutive banks in the dot-product loops.  16-byte stores, no conflicts.
-template <int NT>
-KC_D void stage96(float* __restrict__ dst, const float* __restrict__ src, int rows, int tid) {
-  const int n4 = rows * 24;
-  for(int q = tid; q < n4; q += NT)
-    reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(src)[q];
-}
-
 // The residual trunk is f32.  Between blocks it lives in the accumulators; while
 // a block's first convolution owns them it is parked in a workgroup-private global
 // scratch in accumulator-fragment order (1 KiB contiguous per wave and tile, an
@@ -921,22 +932,33 @@ KC_D void zeroBorders(uint16_t* act, int tid) {
 // KataGPool over 32 f32 channels of scr ([b*A+p][SCR]) per board: mean,
 // mean * (sqrt(A)-14)/10, max (model_pytorch.py:326-352); with vsrc also the value
 // head's mean, mean * (sqrt(A)-14)/10, mean * ((sqrt(A)-14)^2/100 - 0.1).
-// A lane pair per (board, channel), each summing half of the board's cells.
+// A lane pair per (board, channel), each summing half of the board's cells: all of the
+// half's reads are issued before the first add (one LDS latency, not one per cell); the
+// sums run over the cells in order, then half + half.
 template <class G>
 KC_D void poolBoards(const float* scr, const float* vsrc, float* poolP, float* poolV, float sqOff, int tid) {
+  constexpr int H = (G::A + 1) / 2;  // cells of the first half; the second has A - H
   for(int idx = tid; idx < G::NB * 64; idx += G::NT) {
     const int pr = idx >> 1, half = idx & 1;
     const int b = pr >> 5, c = pr & 31;
-    const int p0 = half ? (G::A + 1) / 2 : 0, p1 = half ? G::A : (G::A + 1) / 2;
-    float s = 0.0f, m = 0.0f, sv = 0.0f;
-#pragma unroll 4
-    for(int p = p0; p < p1; p++) {
-      const int o = (b * G::A + p) * G::SCR + c;
-      const float v = scr[o];
-      s += v;
-      m = v > m ? v : m;
+    const int cnt = half ? G::A - H : H;
+    const int o0 = (b * G::A + (half ? H : 0)) * G::SCR + c;
+    float v[H], vv[H];
+#pragma unroll
+    for(int i = 0; i < H; i++) {
+      v[i] = i < cnt ? scr[o0 + i * G::SCR] : 0.0f;
       if(vsrc)
-        sv += vsrc[o];
+        vv[i] = i < cnt ? vsrc[o0 + i * G::SCR] : 0.0f;
+    }
+    float s = 0.0f, m = 0.0f, sv = 0.0f;
+#pragma unroll
+    for(int i = 0; i < H; i++) {
+      if(i < cnt) {
+        s += v[i];
+        m = v[i] > m ? v[i] : m;
+        if(vsrc)
+          sv += vv[i];
+      }
     }
     s = s + asF(partner<5>(bitsF(s)));  // lane ^ 1 (DPP)
     m = fmaxf(m, asF(partner<5>(bitsF(m))));
@@ -1046,10 +1068,68 @@ KC_D void linear96(const float* wT, int O, const float* in, float* out, int ostr
   }
 }
 
+// The heads' two linears at once: the value linear (O = 64, a wave per board) on items
+// [0, NB * 64), the policy-gpool linear (O = 32, half a wave per board) on the NB * 32
+// after them -- disjoint waves (NB * 64 is a multiple of the wave).  An item is computed
+// exactly as linear96 computes it: 24 sequential s += w * x per quarter, the quarters
+// combined as (q0 + q1) + (q2 + q3) across lanes.
+template <int O>
+KC_D void linear96Item(const float* wT, const float* in, float* out, const float* bias, bool relu, int idx) {
+  static_assert(O == 64 || O == 32, "a board's items are a wave or an aligned half of one");
+  constexpr int quads = O >> 2;
+  const int q = idx & (quads - 1), ks = (idx / quads) & 3, b = idx / (4 * quads);
+  float4 s = float4{0.0f, 0.0f, 0.0f, 0.0f};
+  const float* xi = in + b * 96 + ks * 24;
+  const float* wi = wT + (ks * 24) * O + 4 * q;
+#pragma unroll 4
+  for(int i = 0; i < 24; i++) {
+    const float4 w4 = *reinterpret_cast<const float4*>(wi + i * O);
+    const float xv = xi[i];
+    s.x += w4.x * xv;
+    s.y += w4.y * xv;
+    s.z += w4.z * xv;
+    s.w += w4.w * xv;
+  }
+  float r[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+  for(int j = 0; j < 4; j++) {
+    int a0, a1;
+    if(O == 64) {  // lanes 16 then 32 apart (permlane swaps)
+      swapPair<1>(bitsF(r[j]), a0, a1);
+      r[j] = asF(a0) + asF(a1);
+      swapPair<0>(bitsF(r[j]), a0, a1);
+      r[j] = asF(a0) + asF(a1);
+    } else {  // lane ^8 (row rotation by 8), then 16 apart
+      r[j] += asF(partner<2>(bitsF(r[j])));
+      swapPair<1>(bitsF(r[j]), a0, a1);
+      r[j] = asF(a0) + asF(a1);
+    }
+  }
+  if(ks == 0) {
+#pragma unroll
+    for(int j = 0; j < 4; j++) {
+      const float v = bias ? bias[4 * q + j] + r[j] : r[j];
+      out[b * O + 4 * q + j] = relu ? fmaxf(v, 0.0f) : v;
+    }
+  }
+}
+template <class G>
+KC_D void headLinears(const float* plgT, const float* poolP, float* biasS, const float* l2T, const float* poolV,
+                      float* vh, const float* vB2, int tid) {
+  for(int idx = tid; idx < G::NB * 96; idx += G::NT) {
+    if(idx < G::NB * 64)
+      linear96Item<64>(l2T, poolV, vh, vB2, true, idx);
+    else
+      linear96Item<32>(plgT, poolP, biasS, nullptr, false, idx - G::NB * 64);
+  }
+}
+
 // Element `tid` of parameter slab k: block k's BN1/BN2 scale+bias and gpool BN
 // ([0,96) bn1s [96,192) bn1b [192,288) bn2s [288,384) bn2b [384,416) bngs
-// [416,448) bngb), or for k == nblocks the tip BN and head biases ([0,96) tips
-// [96,192) tipb [192,224) pBiasG [224,256) vBias1 [256,288) pBias2).  The slabs are
+// [416,448) bngb), for k == nblocks the tip BN, the head biases and the policy's second
+// conv ([0,96) tips [96,192) tipb [192,224) pBiasG [224,256) vBias1 [256,288) pBias2
+// [288,416) pConv2), or for k == nblocks + 1 the head slab ([0,2 v2) vLin3 [2 v2,4 v2)
+// vLinM, then vB3[2] vBM[2], then [4 v2 + 4, 5 v2 + 4) vB2; v2 <= 64).  The slabs are
 // gathered on the host (paramSlabSource), so this is one coalesced load: the per-thread
 // source arithmetic it replaces stayed live across the block loop and, in the
 // register-capped corrected instance, was spilled and reloaded behind the weight DMA.
@@ -1067,7 +1147,16 @@ static int paramSlabSource(const NNLayout& L, int k, int tid) {
     if(tid < NN_PRM && L.kinds[k] == 1) return (f == 4 ? L.bngs[k] : L.bngb[k]) + i;
     return -1;
   }
-  if(tid >= 288) return -1;
+  if(k == L.nblocks + 1) {
+    const int v2 = L.v2;
+    if(tid < 2 * v2) return L.vLin3 + tid;
+    if(tid < 4 * v2) return L.vLinM + tid - 2 * v2;
+    if(tid < 4 * v2 + 2) return L.vB3 + tid - 4 * v2;
+    if(tid < 4 * v2 + 4) return L.vBM + tid - 4 * v2 - 2;
+    if(tid < 5 * v2 + 4) return L.vB2 + tid - 4 * v2 - 4;
+    return -1;
+  }
+  if(tid >= 288) return tid < 288 + 4 * L.p1 && tid < 416 ? L.pConv2 + tid - 288 : -1;
   if(tid < 96) return L.tips + tid;
   if(tid < 192) return L.tipb + tid - 96;
   if(tid < 224) return L.pBiasG + tid - 192;
@@ -1090,7 +1179,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
   // only when one of them is flagged (and clears the flags), else exits at once
   using G = NNGeo<X, Y, C, NB, MODE, BL>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  NN_PHASE(0);
+  NN_PHASE_ENTRY();
   const int count = countDev ? min(*countDev, n) : n;
   const int base = blockIdx.x * G::NB;
   if(base >= count)
@@ -1106,6 +1195,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
     if(!hotMask)
       return;  // uniform: every thread read the same flags
   }
+  NN_PHASE_ENTRY_COMMIT();
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int rg = wave >> 1, cg = wave & 1;
   const int tstart = rg * G::MAXT;
@@ -1120,6 +1210,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
   uint16_t* rowBP = rowPa + G::MROWS;                                 // [MROWS] b*A+p (0xFFFF: padding)
   float* prm = reinterpret_cast<float*>(smem + G::OFF_PRM);  // [2][NPRM] parameter slabs
   h16x8* wl = reinterpret_cast<h16x8*>(smem + G::OFF_W);
+  int* dstRow = reinterpret_cast<int*>(smem + G::OFF_DST);  // [NB] the boards' batch rows
   const float sqOff = sqrtf((float)G::A) - 14.0f;
 
   // the stem's first weight taps (as many as the ring prefetches) stream into the ring
@@ -1152,12 +1243,15 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
   __syncthreads();
   {
     // wave w unpacks board w: its row index and all its packed words are loaded up
-    // front (two round trips), then lane l sets bits l, l+64, ... (plane-major bits)
+    // front (two round trips), then lane l sets bits l, l+64, ... (plane-major bits).
+    // The row is kept in LDS for the output stores at the end.
     static_assert(G::NB <= G::NW, "one wave per board");
     constexpr int NBITS = G::A * NUM_SPATIAL, NWD = (NBITS + 63) / 64;
     const int b = __builtin_amdgcn_readfirstlane(wave);
     if(b < nb) {
       const int src = rowIdx ? rowIdx[base + b] : base + b;
+      if(lane == 0)
+        dstRow[b] = src;
       uint64_t words[NWD];
 #pragma unroll
       for(int k = 0; k < NWD; k++)
@@ -1286,6 +1380,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
     } else {
       // g branch: BN-ReLU into scr (f32, aliases the dead conv input), then
       // KataGPool per board (model_pytorch.py:326-352)
+      NN_PHASE(49);
       const float* gs = P + 384;
       const float* gbias = P + 416;
       // the gpool linear weights ([96][Cr] f32) are requested now and land in LDS
@@ -1375,6 +1470,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
           acc[t][ct] = tr[t][ct];
       waitVm<0>();
       __syncthreads();
+      NN_PHASE(55);
       NN_PHASE(6 + 4 * blk);
       if constexpr(G::BL)
         convTilesB<G, 9, (G::C - 32) / 32, 0>(act, WB + L->wConv2[blk], wl, acc, rb, vm, cg, lane, tid, nextW,
@@ -1391,6 +1487,25 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
   __syncthreads();
   NN_PHASE(40);
   const float* PT = prm + (L->nblocks & 1) * G::NPRM;  // tip slab
+  // everything the heads read from global is requested here, a BN pass and the head conv
+  // ahead of its use: the head slab (value / misc output weights and biases, the value
+  // linear's bias) and the two head linears' transposed weights (32 and v2 rows of 96 f32,
+  // contiguous float4 per thread; stored to the ring once the head conv has left it)
+#pragma unroll
+  for(int j = 0; j < NPK; j++)
+    pre[j] = loadParam(L, WF, L->nblocks + 1, tid + j * G::NT);
+  constexpr int HW = ((32 + 64) * 24 + G::NT - 1) / G::NT;  // float4 per thread (v2 <= 64)
+  float4 hw[HW];
+  {
+    const float4* srcP = reinterpret_cast<const float4*>(WF + L->pLinG);
+    const float4* srcV = reinterpret_cast<const float4*>(WF + L->vLin2);
+    const int nV = L->v2 * 24;
+#pragma unroll
+    for(int k = 0; k < HW; k++) {
+      const int q = tid + k * G::NT;
+      hw[k] = q < 32 * 24 ? srcP[q] : (q - 32 * 24 < nV ? srcV[q - 32 * 24] : float4{0.0f, 0.0f, 0.0f, 0.0f});
+    }
+  }
   storeBnRelu<G>(act, rowPa, acc, PT, PT + 96, tstart, cg, lane, hot, base, nb);
   waitVm<0>();
   __syncthreads();
@@ -1404,6 +1519,24 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
                                             9 + 18 * L->nblocks);
   __syncthreads();  // act dead from here: f32 [MROWS][SCR] value branch at actF, g branch at scr
   NN_PHASE(41);
+  // the ring is idle too: the head linears' weights land in its front (published by the
+  // stage epilogue's barrier below; scr, where it is a ring slot, is slot 1)
+  float* plgT = reinterpret_cast<float*>(wl);
+  float* l2T = plgT + 32 * 96;
+  // the head slab, in the idle parameter slab: value / misc output weights [4][v2], their
+  // 4 biases, then the value linear's v2 biases
+  float* w3 = prm + ((L->nblocks + 1) & 1) * G::NPRM;
+  static_assert(4 * 64 + 4 + 64 <= G::NPRM, "value weights and biases fit a parameter slab");
+#pragma unroll
+  for(int j = 0; j < NPK; j++)
+    if(tid + j * G::NT < G::NPRM)
+      w3[tid + j * G::NT] = pre[j];
+#pragma unroll
+  for(int k = 0; k < HW; k++) {
+    const int q = tid + k * G::NT;
+    if(q < (32 + 64) * 24)
+      reinterpret_cast<float4*>(plgT)[q] = hw[k];  // l2T follows plgT
+  }
   {
     const float* pbg = PT + 192;
     const float* vb1 = PT + 224;
@@ -1429,32 +1562,21 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
   }
   __syncthreads();
   NN_PHASE(53);
-  float* plgT = reinterpret_cast<float*>(wl);
-  float* l2T = plgT + 32 * 96;
-  // value / misc output weights [4][v2], then their 4 biases: in the idle parameter slab
-  float* w3 = prm + ((L->nblocks + 1) & 1) * G::NPRM;
-  static_assert(4 * 64 + 4 <= G::NPRM, "value weights fit a parameter slab");
-  stage96<G::NT>(plgT, WF + L->pLinG, 32, tid);
-  stage96<G::NT>(l2T, WF + L->vLin2, L->v2, tid);
-  {
-    const int v2 = L->v2;
-    for(int i = tid; i < 4 * v2 + 4; i += G::NT) {
-      float w;
-      if(i < 2 * v2)
-        w = WF[L->vLin3 + i];
-      else if(i < 4 * v2)
-        w = WF[L->vLinM + i - 2 * v2];
-      else
-        w = i - 4 * v2 < 2 ? WF[L->vB3 + i - 4 * v2] : WF[L->vBM + i - 4 * v2 - 2];
-      w3[i] = w;
-    }
-  }
+  NN_PHASE(56);
   poolBoards<G>(scr, actF, poolP, poolV, sqOff, tid);
   __syncthreads();
   NN_PHASE(54);
-  linear96<G>(plgT, 32, poolP, biasS, 32, nullptr, false, tid);
-  linear96<G>(l2T, L->v2, poolV, vh, 64, WF + L->vB2, true, tid);
+  if(L->v2 == 64) {
+    // both linears at once, on disjoint waves
+    headLinears<G>(plgT, poolP, biasS, l2T, poolV, vh, w3 + 4 * 64 + 4, tid);
+    NN_PHASE(57);
+  } else {
+    linear96<G>(plgT, 32, poolP, biasS, 32, nullptr, false, tid);
+    NN_PHASE(57);
+    linear96<G>(l2T, L->v2, poolV, vh, 64, w3 + 4 * L->v2 + 4, true, tid);
+  }
   __syncthreads();
+  NN_PHASE(58);
   {
     // value (2) and misc (2) outputs: a 16-lane group per (board, output), each lane
     // summing every 16th term, reduced across the group
@@ -1472,8 +1594,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
     s += asF(partner<4>(bitsF(s)));
     s += asF(partner<5>(bitsF(s)));
     if(k == 0 && b < nb && ((hotMask >> b) & 1u)) {
-      const int dst = rowIdx ? rowIdx[base + b] : base + b;
-      out[(size_t)dst * (G::P + 4) + G::P + o] = s + w3[4 * v2 + o];
+      out[(size_t)dstRow[b] * (G::P + 4) + G::P + o] = s + w3[4 * v2 + o];
     }
   }
   NN_PHASE(42);
@@ -1482,7 +1603,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
     // Channels 0..31 live in column tiles 0 and 1: 8 per lane, reduced over the
     // four lane groups (lane >> 4).
     const float* pb2 = PT + 256;
-    const float* w2 = WF + L->pConv2;
+    const float* w2 = PT + 288;  // the 128 p1 -> 4 conv weights, in the tip slab
     const int c0 = chOf<G>(0, 0, lane), c1 = chOf<G>(0, 1, lane);
 #pragma unroll
     for(int t = 0; t < G::MAXT; t++) {
@@ -1513,7 +1634,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
       }
       if((lane >> 4) == 0 && row < G::ROWS && brd < nb && ((hotMask >> brd) & 1u)) {
         const int pp = bp - brd * G::A;
-        float* o = out + (size_t)(rowIdx ? rowIdx[base + brd] : base + brd) * (G::P + 4);
+        float* o = out + (size_t)dstRow[brd] * (G::P + 4);
 #pragma unroll
         for(int d = 0; d < 4; d++)
           o[d * G::A + pp] = part[d];
@@ -1522,6 +1643,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
   }
   if(G::MODE == NN_MODE_SPLIT3 && hot && tid < nb)
     hot[base + tid] = 0;  // this workgroup re-evaluated its boards (one was flagged)
+  NN_PHASE(59);
 }
 
 #ifndef KC_NN_KERNEL_ONLY
@@ -1869,7 +1991,7 @@ void NNEngine::build(const ModelHost& m, int path) {
     return off;
   };
   // a [rows][96] linear layer stored transposed ([96][rows]): the kernel copies it
-  // into LDS as is (stage96), the layout its dot products read
+  // into LDS as is, the layout its dot products read
   auto f32T = [&](const std::vector<float>& v, int rows) {
     std::vector<float> t(v.size());
     for(int r = 0; r < rows; r++)
@@ -1933,8 +2055,8 @@ void NNEngine::build(const ModelHost& m, int path) {
   L.vLinM = f32(m.vLinM);
   L.vBM = f32(m.vBM);
   {
-    std::vector<float> slabs((size_t)(L.nblocks + 1) * NN_PRM);
-    for(int k = 0; k <= L.nblocks; k++)
+    std::vector<float> slabs((size_t)(L.nblocks + 2) * NN_PRM);
+    for(int k = 0; k <= L.nblocks + 1; k++)
       for(int t = 0; t < NN_PRM; t++) {
         const int src = paramSlabSource(L, k, t);
         slabs[(size_t)k * NN_PRM + t] = src >= 0 ? wf[src] : 0.0f;
