@@ -33,6 +33,7 @@
 #include <functional>
 #include <mutex>
 #include <set>
+#include <string>
 #include <vector>
 
 #include "engine.h"
@@ -1075,29 +1076,51 @@ template <bool SPLIT>
 constexpr bool kConv1PipeFor = !SPLIT;
 #endif
 
+constexpr size_t L_LDS_BUDGET = 160 * 1024;
+
+// Dynamic LDS of a conv's launch, and whether a 1x1 takes the pipelined kernel.  The
+// constructor evaluates it for every conv of the net, so a net too wide for the budget is
+// refused there and not in the middle of a forward.
+template <int X, int Y>
+size_t convLds(int kt, int tn, int wn, bool split, int cin, int gbLd, bool* pipe) {
+  using G = LGeo<X, Y>;
+  const size_t prm = (2 * (size_t)cin + (size_t)G::BPW * (gbLd > 0 ? gbLd : 0)) * 4;
+  *pipe = false;
+  if(kt == 1) {
+    const size_t lp = split ? l1pLds<X, Y, true>(cin) : l1pLds<X, Y, false>(cin);
+    if((split ? kConv1PipeFor<true> : kConv1PipeFor<false>) && lp <= L_LDS_BUDGET) {
+      *pipe = true;
+      return lp;
+    }
+    return (split ? 2 * (size_t)l1StageBytes<G, true>() : (size_t)l1StageBytes<G, false>()) + 2 * (size_t)cin * 4;
+  }
+  if(kConvLdsB && !split && wn == 2)
+    return 2 * (size_t)G::stage(false) + 2 * 3 * (size_t)tn * wn * 1024 + prm;
+  return 2 * (split ? 2 : 1) * (size_t)G::stage(split) + prm;
+}
+
+size_t convLdsAt(int X, int kt, int tn, int wn, bool split, int cin, int gbLd) {
+  bool pipe;
+  return X == 5 ? convLds<5, 5>(kt, tn, wn, split, cin, gbLd, &pipe)
+                : X == 7 ? convLds<7, 7>(kt, tn, wn, split, cin, gbLd, &pipe)
+                         : convLds<9, 9>(kt, tn, wn, split, cin, gbLd, &pipe);
+}
+
 template <int X, int Y, int KT, int TN, bool SPLIT, int WN>
 void launchConvT(const LConvArgs& a, int grid, hipStream_t st) {
-  using G = LGeo<X, Y>;
-  size_t lds;
   const void* fnp;
+  bool pipe;
+  const size_t lds = convLds<X, Y>(KT, TN, WN, SPLIT, a.cin, a.gbLd, &pipe);
   if constexpr(KT == 1) {
     if(a.pro != PRO_BN)
       throw std::invalid_argument("1x1 convolutions take a BN-ReLU prologue");
-    if(kConv1PipeFor<SPLIT> && l1pLds<X, Y, SPLIT>(a.cin) <= 160 * 1024) {
-      lds = l1pLds<X, Y, SPLIT>(a.cin);
-      fnp = (const void*)kConv1LP<X, Y, TN, SPLIT, WN>;
-    } else {
-      lds = (SPLIT ? 2 : 1) * l1StageBytes<G, SPLIT>() + 2 * (size_t)a.cin * 4;
-      fnp = (const void*)kConv1L<X, Y, TN, SPLIT, WN>;
-    }
+    fnp = pipe ? (const void*)kConv1LP<X, Y, TN, SPLIT, WN> : (const void*)kConv1L<X, Y, TN, SPLIT, WN>;
   } else if constexpr(kConvLdsB && !SPLIT && WN == 2) {
-    lds = 2 * G::stage(SPLIT) + 2 * 3 * TN * WN * 1024 + (2 * a.cin + G::BPW * (a.gbLd > 0 ? a.gbLd : 0)) * 4;
     fnp = (const void*)kConvLB<X, Y, TN, WN>;
   } else {
-    lds = 2 * (SPLIT ? 2 : 1) * G::stage(SPLIT) + (2 * a.cin + G::BPW * (a.gbLd > 0 ? a.gbLd : 0)) * 4;
     fnp = (const void*)kConvL<X, Y, KT, TN, SPLIT, WN>;
   }
-  if(lds > 160 * 1024)
+  if(lds > L_LDS_BUDGET)
     throw std::invalid_argument("layered conv: LDS budget exceeded");
   static std::mutex mu;
   // (device, kernel) pairs whose attribute is set (per device; an instance may
@@ -1108,7 +1131,7 @@ void launchConvT(const LConvArgs& a, int grid, hipStream_t st) {
   {
     std::lock_guard<std::mutex> lk(mu);
     if(!done.count({dev, fnp})) {
-      KC_HIP(hipFuncSetAttribute(fnp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      KC_HIP(hipFuncSetAttribute(fnp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L_LDS_BUDGET));
       done.insert({dev, fnp});
     }
   }
@@ -1191,9 +1214,37 @@ NNLayered::NNLayered(const ModelHost& m, int X, int Y, int W, bool split)
     : cfg_(m.cfg), X_(X), Y_(Y), W_(W), split_(split) {
   if(!supportedGeometry(X, Y))
     throw std::invalid_argument("NNLayered: board geometry must be 5x5, 7x7 or 9x9");
-  if(cfg_.gin != 1 || cfg_.cin > 32 || cfg_.p1 > 64 || cfg_.g1 > 64 || cfg_.v1 > 128 || cfg_.v2 > 256 ||
-     cfg_.Cg > 128)
-    throw std::invalid_argument("NNLayered: head/gpool widths out of range");
+  // What the kernels index (DESIGN.md §5 "Widths the layered kernels take"): kHeadsL's and
+  // kGpoolBias's LDS arrays bound the head and gpool widths; the conv epilogue stores (and
+  // the prologue loads) four f32 channels of a row at a time from X [rows][C] and
+  // Y [rows][mid], so those two leading dimensions must be multiples of 4 -- otherwise the
+  // last store of a row is misaligned and runs into the next row, which another lane owns.
+  // Every other width is free: K slices and output tiles are padded and guarded.
+  auto refuse = [](const char* what, int v, const char* rule) {
+    throw std::invalid_argument(std::string("NNLayered: ") + what + " = " + std::to_string(v) + " is not supported: " +
+                                rule);
+  };
+  if(cfg_.gin != 1)
+    refuse("global inputs", cfg_.gin, "the stem takes exactly 1");
+  if(cfg_.cin > 32)
+    refuse("input planes", cfg_.cin, "at most 32");
+  if(cfg_.p1 > 64)
+    refuse("policy width p1", cfg_.p1, "at most 64");
+  if(cfg_.g1 > 64)
+    refuse("policy gpool width g1", cfg_.g1, "at most 64");
+  if(cfg_.v1 > 128)
+    refuse("value width v1", cfg_.v1, "at most 128");
+  if(cfg_.v2 > 256)
+    refuse("value width v2", cfg_.v2, "at most 256");
+  if(cfg_.Cg > 128)
+    refuse("gpool width Cg", cfg_.Cg, "at most 128");
+  if(cfg_.C % 4 != 0)
+    refuse("trunk width C", cfg_.C, "a multiple of 4 (any multiple: K slices and output tiles are padded)");
+  bool nested = false;
+  for(int k : cfg_.kinds)
+    nested = nested || k >= 2;
+  if(nested && cfg_.mid % 4 != 0)
+    refuse("bottleneck width mid", cfg_.mid, "a multiple of 4");
   const int A = X * Y;
   std::vector<uint16_t> wh, wl;  // fragments (8 fp16 each), hi / lo
   std::vector<float> wf;
@@ -1210,6 +1261,15 @@ NNLayered::NNLayered(const ModelHost& m, int X, int Y, int W, bool split)
       for(int i = 0; i < I; i++)
         t[(size_t)i * O + o] = w[(size_t)o * I + i];
     return t;
+  };
+  // a conv whose stage, weight ring and per-channel parameters pass the LDS budget at this
+  // geometry cannot run (gbLd: the per-board gpool bias a gpool block's conv2 also keeps there)
+  auto fits = [&](const Conv& c, int gbLd) {
+    const size_t need = convLdsAt(X, c.kt, c.tn, c.wn, split_, c.cin, gbLd);
+    if(need > L_LDS_BUDGET)
+      throw std::invalid_argument("NNLayered: a " + std::to_string(c.cinReal) + " -> " + std::to_string(c.cout) +
+                                  " convolution needs " + std::to_string(need) + " bytes of LDS at this board size, " +
+                                  std::to_string(L_LDS_BUDGET) + " are available: the net is too wide");
   };
   // Conv weights W(co, ci, tap) -> fragments [cb][tap][ct][lane][8]
   auto packConvL = [&](int kt, int cin, int cout, const std::function<float(int, int, int)>& Wf) {
@@ -1236,6 +1296,7 @@ NNLayered::NNLayered(const ModelHost& m, int X, int Y, int W, bool split)
               wh.push_back(h);
               wl.push_back(lf2h(v - (float)hf));
             }
+    fits(c, 0);
     return c;
   };
   auto conv3 = [&](const std::vector<float>& w, int cin, int cout) {
@@ -1279,6 +1340,7 @@ NNLayered::NNLayered(const ModelHost& m, int X, int Y, int W, bool split)
       o.bn2s = f32(b.bn2s);
       o.bn2b = f32(b.bn2b);
       o.conv2 = conv3(b.conv2, Cr, Wd);
+      fits(o.conv2, Cr);
     }
   };
   const int C = cfg_.C;
@@ -1347,6 +1409,11 @@ void NNLayered::ensure(int n) {
   // X f32 [rows][C] | Y f32 [rows][mid] | T f32 [rows][tW] | H f16 [rows][hW] | gb f32 [nPad][C]
   const size_t bytes = rows * (cfg_.C + cfg_.mid + tW_) * 4 + rows * hW_ * 2 + (size_t)nPad * maxW_ * 4 + 256;
   KC_HIP(hipMalloc(&act_, bytes));
+  // H's channels [width, next multiple of 32) are read by the fp16 prologue (PRO_F16 has no
+  // channel guard; their weights are zero) and written by no epilogue: they must be zeros, not
+  // whatever the allocation held (0 x NaN = NaN).  Once per allocation, off the hot path.
+  KC_HIP(hipMemset(act_, 0, bytes));
+  KC_HIP(hipStreamSynchronize(nullptr));  // forward's stream need not order after the null stream
   char* p = reinterpret_cast<char*>(act_);
   bufX_ = reinterpret_cast<float*>(p);
   p += rows * cfg_.C * 4;

@@ -214,3 +214,4 @@ def test_layered_trained_net_within_north_star(arch, X, Y, W, steps):
     print("%s %dx%d after %d steps: max |logit| %.2f, default (split) vs fp32 %.3e, fast-layered %.3e" %
           (arch, X, Y, steps, np.abs(ref).max(), err, err_f))
     assert err <= 1e-3
+    assert err < err_f  # the split kernels are nearer fp32 than the fp16 ones (test_gpu_nn_split.py has the sharp bound)
