@@ -402,7 +402,9 @@ typedef struct coffee_match_stats {
  * move temperature 0.5 early / 0.2 with halflife 19, LCB on at 5.0 / 0.15, root FPU
  * reduction 0.1, subtree value bias 0.35; what that config leaves at the reference's
  * defaults: root noise off, root policy temperatures 1, no desired-per-child visits, one
- * root symmetry.  Every play setting off.  Other fields as coffee_search_params_default. */
+ * root symmetry.  Every play setting off.  Other fields as coffee_search_params_default.
+ * That config's useUncertainty (:108-110) is not a field of this struct: uncertainty via
+ * coffee_match_set_uncertainty (off unless set). */
 void coffee_match_params_default(coffee_search_params* p);
 int coffee_match_create(const coffee_match_config* cfg, coffee_match** out);
 /* As coffee_selfplay_step / _sync / _stream / _destroy. */
@@ -537,6 +539,38 @@ int coffee_analysis_game_info(coffee_analysis* h, int slot, int64_t* info);
 int coffee_analysis_game_tree(coffee_analysis* h, int slot, int max_nodes, uint32_t* nodes, uint32_t* edges,
                               int* n_nodes);
 int coffee_analysis_root_policy(coffee_analysis* h, int slot, float* out);
+
+/* ---- uncertainty weighting of playouts (the reference's useUncertainty) ----
+ * An evaluation whose short-term win/loss error the net predicts to be large counts for less
+ * in every average above it (Search::computeWeightFromNNOutput, searchupdatehelpers.cpp:98-120):
+ *   x   = the row's output [P+3] (the shorttermWinlossError logit)
+ *   s   = 0.5 x > 40 ? 0.5 x : log(1 + exp(0.5 x))          (nneval.cpp:789-793)
+ *   err = sqrt(s * s * 0.25)
+ *   p   = err for exponent 1, sqrt(err) for 0.5, else err ^ exponent
+ *   w   = coeff / (p + coeff / max_weight)
+ * in f32 with the search's deterministic log / exp / pow.  The node's own evaluation enters its
+ * weight_sum, weight_sq_sum and averages with weight w instead of 1, a terminal visit with
+ * max_weight.  Off (the default of all three engines), every weight is 1 and nothing changes.
+ * The setting is not a coffee_search_params field because that struct keeps its layout. */
+typedef struct coffee_uncertainty_params {
+  int32_t use_uncertainty;          /* 0 */
+  float uncertainty_coeff;          /* 0.25, range [1e-4, 1]  (setup.cpp:546) */
+  float uncertainty_exponent;       /* 1.0,  range [0, 2] */
+  float uncertainty_max_weight;     /* 8.0,  range [1, 100] */
+} coffee_uncertainty_params;
+void coffee_uncertainty_params_default(coffee_uncertainty_params* p);
+/* The formulas above on the host (no device is touched), bit for bit what the search kernels
+ * compute: *err and *weight of one logit (either may be NULL).  With use_uncertainty 0 the
+ * weight is 1.  COFFEE_EINVAL for out-of-range or non-finite parameters. */
+int coffee_uncertainty_weight(const coffee_uncertainty_params* p, float st_error_logit, float* err, float* weight);
+/* Sets the weighting of an engine; in a match one setting serves both nets (gatekeeper1.cfg:
+ * 108-110).  Only before the engine's first round, and for analysis before the first query is
+ * submitted: a tree never mixes the two rules.  Afterwards, or for out-of-range or non-finite
+ * values, COFFEE_EINVAL without touching the device.  With the setting on, word 21 of each
+ * coffee_*_game_tree node holds the f32 bits of the node's own evaluation weight (off: 0). */
+int coffee_selfplay_set_uncertainty(coffee_selfplay* h, const coffee_uncertainty_params* p);
+int coffee_match_set_uncertainty(coffee_match* h, const coffee_uncertainty_params* p);
+int coffee_analysis_set_uncertainty(coffee_analysis* h, const coffee_uncertainty_params* p);
 
 /* Writes n rows (HOST arrays, drain_rows layout) as a training .npz in the reference's
  * format (TrainingWriteBuffers::writeToZipFile trainingwrite.cpp:566-587): members

@@ -124,6 +124,11 @@ class MatchStats(ctypes.Structure):
                 ("nn_audit_switches", ctypes.c_uint64 * 2), ("nn_audit_max_diff", ctypes.c_double * 2)]
 
 
+class UncertaintyParams(ctypes.Structure):
+    _fields_ = [("use_uncertainty", ctypes.c_int32), ("uncertainty_coeff", ctypes.c_float),
+                ("uncertainty_exponent", ctypes.c_float), ("uncertainty_max_weight", ctypes.c_float)]
+
+
 ANALYSIS_MAX_MOVES = 100
 ANALYSIS_MAX_PV = 16
 ANALYSIS_OK, ANALYSIS_ILLEGAL_MOVE, ANALYSIS_GAME_OVER, ANALYSIS_NO_LEGAL_MOVE = 0, 1, 2, 3
@@ -189,6 +194,8 @@ EXPORTS = [
     "coffee_analysis_stream", "coffee_analysis_destroy", "coffee_analysis_submit", "coffee_analysis_query_check",
     "coffee_analysis_drain", "coffee_analysis_stats_get", "coffee_analysis_game_info", "coffee_analysis_game_tree",
     "coffee_analysis_root_policy",
+    "coffee_uncertainty_params_default", "coffee_uncertainty_weight", "coffee_selfplay_set_uncertainty",
+    "coffee_match_set_uncertainty", "coffee_analysis_set_uncertainty",
 ]
 
 
@@ -279,6 +286,12 @@ def lib():
         L.coffee_analysis_game_info.argtypes = [c_p, c_i, c_p]
         L.coffee_analysis_game_tree.argtypes = [c_p, c_i, c_i, c_p, c_p, c_p]
         L.coffee_analysis_root_policy.argtypes = [c_p, c_i, c_p]
+        L.coffee_uncertainty_params_default.argtypes = [c_p]
+        L.coffee_uncertainty_params_default.restype = None
+        L.coffee_uncertainty_weight.argtypes = [c_p, ctypes.c_float, c_p, c_p]
+        L.coffee_selfplay_set_uncertainty.argtypes = [c_p, c_p]
+        L.coffee_match_set_uncertainty.argtypes = [c_p, c_p]
+        L.coffee_analysis_set_uncertainty.argtypes = [c_p, c_p]
         _lib = L
     return _lib
 
@@ -318,6 +331,34 @@ def default_analysis_params(**over):
     for k, v in over.items():
         setattr(p, k, v)
     return p
+
+
+def default_uncertainty_params(**over):
+    """coffee_uncertainty_params_default: off, coefficient 0.25, exponent 1, maximum weight 8
+    (gatekeeper1.cfg:108-110 turns it on with these values)."""
+    p = UncertaintyParams()
+    lib().coffee_uncertainty_params_default(ctypes.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def _uncertainty_params(params, over):
+    p = default_uncertainty_params() if params is None else UncertaintyParams.from_buffer_copy(params)
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def uncertainty_weight(logit, params=None, **over):
+    """(err, weight) of one short-term error logit (a network row's out[P+3]) as np.float32:
+    coffee_uncertainty_weight, the host run of the search kernels' own sequence.  params: an
+    UncertaintyParams (default: default_uncertainty_params()); keyword overrides on top."""
+    p = _uncertainty_params(params, over)
+    err, w = ctypes.c_float(), ctypes.c_float()
+    check(lib().coffee_uncertainty_weight(ctypes.byref(p), ctypes.c_float(float(logit)), ctypes.byref(err),
+                                          ctypes.byref(w)))
+    return np.float32(err.value), np.float32(w.value)
 
 
 def analysis_queries(queries):
@@ -596,6 +637,13 @@ class Selfplay:
     def step(self, rounds, stream=None):
         check(lib().coffee_selfplay_step(self.h, rounds, stream))
 
+    def set_uncertainty(self, params=None, **over):
+        """Uncertainty weighting of the engine's evaluations (coffee_selfplay_set_uncertainty): an
+        UncertaintyParams and / or its fields as keywords, e.g. use_uncertainty=1.  Only before
+        the first round; afterwards, or for out-of-range values, CoffeeError."""
+        p = _uncertainty_params(params, over)
+        check(lib().coffee_selfplay_set_uncertainty(self.h, ctypes.byref(p)))
+
     def sync(self):
         check(lib().coffee_selfplay_sync(self.h))
 
@@ -758,6 +806,13 @@ class Match:
     def step(self, rounds, stream=None):
         check(lib().coffee_match_step(self.h, rounds, stream))
 
+    def set_uncertainty(self, params=None, **over):
+        """Uncertainty weighting of the engine's evaluations (coffee_match_set_uncertainty): an
+        UncertaintyParams and / or its fields as keywords, e.g. use_uncertainty=1.  Only before
+        the first round (one setting serves both nets); afterwards, or for out-of-range values, CoffeeError."""
+        p = _uncertainty_params(params, over)
+        check(lib().coffee_match_set_uncertainty(self.h, ctypes.byref(p)))
+
     def sync(self):
         check(lib().coffee_match_sync(self.h))
 
@@ -866,6 +921,13 @@ class Analysis:
 
     def step(self, rounds, stream=None):
         check(lib().coffee_analysis_step(self.h, rounds, stream))
+
+    def set_uncertainty(self, params=None, **over):
+        """Uncertainty weighting of the engine's evaluations (coffee_analysis_set_uncertainty): an
+        UncertaintyParams and / or its fields as keywords, e.g. use_uncertainty=1.  Only before
+        the first submitted query and round; afterwards, or for out-of-range values, CoffeeError."""
+        p = _uncertainty_params(params, over)
+        check(lib().coffee_analysis_set_uncertainty(self.h, ctypes.byref(p)))
 
     def sync(self):
         check(lib().coffee_analysis_sync(self.h))

@@ -718,6 +718,51 @@ int coffee_selfplay_root_policy(coffee_selfplay* h, int slot, float* out) {
   });
 }
 
+// ---- uncertainty weighting (uncertainty.h: the sequences the search kernels run) ----
+
+void coffee_uncertainty_params_default(coffee_uncertainty_params* p) {
+  if(!p)
+    return;
+  // searchparams.cpp:29-32 (off), gatekeeper1.cfg:108-110 / setup.cpp:539-562 values
+  p->use_uncertainty = 0;
+  p->uncertainty_coeff = 0.25f;
+  p->uncertainty_exponent = 1.0f;
+  p->uncertainty_max_weight = 8.0f;
+}
+
+int coffee_uncertainty_weight(const coffee_uncertainty_params* p, float st_error_logit, float* err, float* weight) {
+  return guarded([&] {
+    need(p != nullptr, "NULL argument");
+    const Unc u = toUnc(*p);
+    const float e = stErrorOf(st_error_logit);
+    if(err)
+      *err = e;
+    if(weight)
+      *weight = uncWeightOf(u, e);
+  });
+}
+
+int coffee_selfplay_set_uncertainty(coffee_selfplay* h, const coffee_uncertainty_params* p) {
+  return guarded([&] {
+    need(h && h->eng && p, "NULL argument");
+    h->eng->setUncertainty(*p);
+  });
+}
+
+int coffee_match_set_uncertainty(coffee_match* h, const coffee_uncertainty_params* p) {
+  return guarded([&] {
+    need(h && h->eng && p, "NULL argument");
+    h->eng->setUncertainty(*p);
+  });
+}
+
+int coffee_analysis_set_uncertainty(coffee_analysis* h, const coffee_uncertainty_params* p) {
+  return guarded([&] {
+    need(h && h->eng && p, "NULL argument");
+    h->eng->setUncertainty(*p);
+  });
+}
+
 int coffee_debug_cdf_table(int x, int y, int win_len, float* out) {
   return guarded([&] {
     need(out != nullptr, "NULL argument");

@@ -237,6 +237,7 @@ int analysisMain(int argc, char** argv) {
   }
   Settings s;
   coffee_analysis_params_default(&s.sp);
+  coffee_uncertainty_params_default(&s.unc);
   int slots = 64, pvLen = 15;  // analysis_example.cfg: analysisPVLen 15
   try {
     applyConfig(kv, s);
@@ -270,6 +271,7 @@ int analysisMain(int argc, char** argv) {
   c.max_pv_len = pvLen;
   Service sv;
   must(coffee_analysis_create(&c, &sv.h), "create analysis engine");
+  must(coffee_analysis_set_uncertainty(sv.h, &s.unc), "set uncertainty");
   sv.x = s.x;
   sv.y = s.y;
   sv.A = s.x * s.y;

@@ -49,6 +49,10 @@ struct Settings {
   int64_t maxGamesTotal = -1;
   uint64_t seed = 0;
   coffee_search_params sp;
+  // useUncertainty & co: like sp, set to the library's defaults (coffee_uncertainty_params_default:
+  // off) by the command before applyConfig; off unless the config turns it on, for all three
+  // commands (the reference's loader defaults it on for analysis, GTP and match, setup.cpp:539-562)
+  coffee_uncertainty_params unc;
 };
 
 inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& s) {
@@ -178,6 +182,20 @@ inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& 
   getb("recordTreePositions", p.record_tree_positions);
   geti("recordTreeThreshold", p.record_tree_threshold);
   getf("recordTreeTargetWeight", p.record_tree_target_weight);
+  // uncertainty weighting, with the reference's ranges (setup.cpp:539-562); a value outside
+  // them (NaN included) is an error naming the key, like ConfigParser::getDouble(key, min, max)
+  auto getfIn = [&](const char* k, float& v, float lo, float hi) {
+    if(kv.find(k) == kv.end())
+      return;
+    getf(k, v);
+    if(!(v >= lo && v <= hi))
+      throw std::invalid_argument(std::string("config key ") + k + ": value " + std::to_string(v) +
+                                  " outside [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
+  };
+  getb("useUncertainty", s.unc.use_uncertainty);
+  getfIn("uncertaintyCoeff", s.unc.uncertainty_coeff, 0.0001f, 1.0f);
+  getfIn("uncertaintyExponent", s.unc.uncertainty_exponent, 0.0f, 2.0f);
+  getfIn("uncertaintyMaxWeight", s.unc.uncertainty_max_weight, 1.0f, 100.0f);
 }
 
 }  // namespace kccli

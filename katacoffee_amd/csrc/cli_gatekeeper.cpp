@@ -104,6 +104,10 @@ bool gateOnce(const Settings& s, int gamesPerGating, const Dirs& d, bool autoRej
   c.nn_precision = s.nnPrecision;
   coffee_match* h = nullptr;
   must(coffee_match_create(&c, &h), "create match engine");
+  must(coffee_match_set_uncertainty(h, &s.unc), "set uncertainty");  // one setting for both nets
+  if(s.unc.use_uncertainty)
+    logf("gatekeeper: uncertainty weighting on for both nets: coeff %g, exponent %g, max weight %g",
+         s.unc.uncertainty_coeff, s.unc.uncertainty_exponent, s.unc.uncertainty_max_weight);
   logf("gatekeeper: %s (candidate) against %s, %d games on %d slots, %dx%d win %d, %d visits", candName.c_str(),
        baseName.c_str(), N, G, s.x, s.y, s.winLen, s.sp.max_visits);
   const std::string sgfDir = d.sgf + "/" + candName;
@@ -221,6 +225,7 @@ int gatekeeperMain(int argc, char** argv) {
   Settings s;
   s.games = 128;  // gatekeeper1.cfg numGameThreads
   coffee_match_params_default(&s.sp);
+  coffee_uncertainty_params_default(&s.unc);
   int gamesPerGating = 200;  // gatekeeper1.cfg numGamesPerGating
   try {
     applyConfig(kv, s);

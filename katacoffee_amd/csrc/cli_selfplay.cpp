@@ -202,6 +202,10 @@ static void runGpu(int gpu, int server, int perGpu, int slot, int share, const S
   c.nn_precision = s.nnPrecision;
   coffee_selfplay* h = nullptr;
   check(coffee_selfplay_create(&c, &h), "create engine");
+  check(coffee_selfplay_set_uncertainty(h, &s.unc), "set uncertainty");
+  if(s.unc.use_uncertainty)
+    logf("gpu %d.%d: uncertainty weighting on: coeff %g, exponent %g, max weight %g", gpu, server,
+         s.unc.uncertainty_coeff, s.unc.uncertainty_exponent, s.unc.uncertainty_max_weight);
   std::mt19937_64 fileRng(s.seed ^ (0x9E3779B97F4A7C15ULL * (gpu + 1)) ^ ((uint64_t)server << 48));
   auto dirsFor = [&](const std::string& m, std::string& tdata, std::string& sgfs) {
     tdata = outDir + "/" + modelNameOf(m) + "/tdata";
@@ -349,6 +353,7 @@ int main(int argc, char** argv) {
   }
   Settings s;
   coffee_search_params_default(&s.sp);
+  coffee_uncertainty_params_default(&s.unc);
   try {
     applyConfig(kv, s);
   } catch(const std::exception& e) {

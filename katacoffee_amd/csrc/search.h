@@ -23,6 +23,7 @@
 #pragma once
 #include "../../include/katacoffee.h"
 #include "kc_common.h"
+#include "uncertainty.h"
 
 namespace kc {
 
@@ -143,7 +144,9 @@ struct Node {
   uint16_t nextPos;
   uint16_t pad0;
   uint32_t edgeBase;              // the node's block of child slots >= INLINE_EDGES in the edge pool
-  uint32_t pad1;
+  // the weight of the node's own evaluation in its averages (uncertainty weighting, DESIGN.md
+  // 8c; 1 with the setting off), written with nnWin / nnLoss
+  float nnWeight;
 };
 static_assert(sizeof(Node) == 64, "Node layout");
 
@@ -225,6 +228,8 @@ struct GameDev {
   uint32_t syms;                  // four root symmetries, 4 bits each
   int32_t cSlot;                  // NN-cache slot of the leaf (hit or bid)
   float cHitWin, cHitLoss;        // a cache hit's values, read by kSelect with the key
+  float cHitErr;                  // and its short-term error (uncertainty weighting)
+  float accErr;                   // root symmetry accumulation of the short-term error, next to accWin
   int32_t noNoise;                // this move is a cheap search without recorded rows
   int32_t visitLimit;             // this move's maxVisits (getSearchLimitsThisMove)
   float moveWeight;               // this move's target weight
@@ -315,6 +320,7 @@ struct SearchDev {
   DPtr<uint64_t> cKey;        // [entries][2]
   DPtr<float> cPol;           // [entries][P] post-processed policy (illegal = -1)
   DPtr<float> cVal;           // [entries][2] white win / loss
+  DPtr<float> cErr;           // [entries] short-term error (stErrorOf of the evaluation's logit)
   DPtr<uint32_t> cTag;        // [entries] this round's highest bidding game + 1 (0 = none)
   DPtr<uint32_t> cClear;      // [G] fused rounds: slot + 1 whose tag kResolve clears (0 = none)
   DPtr<int32_t> pendList;     // [G] fused rounds: games whose cache lookup waits for kResolve (LEAF_PENDING)
@@ -341,6 +347,8 @@ struct SearchDev {
   DPtr<GameRec> gRec;               // [gCap]
   DPtr<unsigned long long> gCount;
   DPtr<unsigned long long> gDropped;
+  // uncertainty weighting of the evaluations (coffee_*_set_uncertainty; off: every weight 1)
+  Unc unc;
   // two-network match play (the MATCH kernel instantiations; DESIGN.md "Match play"): net 0
   // uses the arrays above, net 1 these.  matchNet() names the net of a game's evaluations.
   int32_t matchMode;
@@ -351,6 +359,7 @@ struct SearchDev {
   DPtr<uint64_t> cKey1;
   DPtr<float> cPol1;
   DPtr<float> cVal1;
+  DPtr<float> cErr1;
   DPtr<uint32_t> cTag1;
   // position analysis (DESIGN.md "Analysis"): a slot holds one query or is idle (phase PH_COMMIT
   // without a commit-list entry, which the round kernels skip).  Queries wait in aQuery, a ring

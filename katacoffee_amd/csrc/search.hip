@@ -334,7 +334,7 @@ KC_D int allocNode(const GV& v, GameDev& s, int nextPla, uint64_t k0, uint64_t k
     n.nextPos = 0xFFFF;
     n.pad0 = 0;
     n.edgeBase = 0;
-    n.pad1 = 0;
+    n.nnWeight = 1.0f;
     v.nodes()[idx] = n;
     v.nodeKey(idx)[0] = k0;
     v.nodeKey(idx)[1] = k1;
@@ -352,7 +352,10 @@ struct NStats {
 };
 
 // oracle addLeafValue (searchupdatehelpers.cpp:12-82); returns the new statistics.
-KC_D NStats addLeafValue(const GV& v, const GameDev& s, int ni, float wl, bool isTerminal, bool assumeNoExisting) {
+// weight: the evaluation's weight (uncertainty weighting; 1 with the setting off, and
+// x * 1.0f is exact, so the one sequence serves both).
+KC_D NStats addLeafValue(const GV& v, const GameDev& s, int ni, float wl, float weight, bool isTerminal,
+                         bool assumeNoExisting) {
   const SP& sp = *v.sp;
   Node* np = &v.nodes()[ni];
   const int svbEntry = np->svbEntry;
@@ -371,15 +374,15 @@ KC_D NStats addLeafValue(const GV& v, const GameDev& s, int ni, float wl, bool i
     winLossAvg = wl;
     utilityAvg = utility;
     utilitySqAvg = usq;
-    weightSqSum = 1.0f;
-    weightSum = 1.0f;
+    weightSqSum = weight * weight;
+    weightSum = weight;
     visits += 1;
   } else {
-    float oldW = weightSum, newW = oldW + 1.0f;
-    winLossAvg = (winLossAvg * oldW + wl) / newW;
-    utilityAvg = (utilityAvg * oldW + utility) / newW;
-    utilitySqAvg = (utilitySqAvg * oldW + usq) / newW;
-    weightSqSum = weightSqSum + 1.0f;
+    float oldW = weightSum, newW = oldW + weight;
+    winLossAvg = (winLossAvg * oldW + wl * weight) / newW;
+    utilityAvg = (utilityAvg * oldW + utility * weight) / newW;
+    utilitySqAvg = (utilitySqAvg * oldW + usq * weight) / newW;
+    weightSqSum = weightSqSum + weight * weight;
     weightSum = newW;
     visits += 1;
   }
@@ -421,7 +424,7 @@ template <int NI>
 struct PathLevel {
   int ni, slot, k, nextPla, svbEntry;
   uint32_t ebase;
-  float nnWin, nnLoss, lastSvbDelta, lastSvbWeight;
+  float nnWin, nnLoss, nnWeight, lastSvbDelta, lastSvbWeight;
   uint32_t visits0;
   uint32_t ech[NI], evis[NI];  // edge child and visits
   uint32_t cv[NI];
@@ -452,6 +455,7 @@ KC_D void loadLevel(const GV& v, int ni, int slot, PathLevel<NI>& L) {
   L.svbEntry = nd.svbEntry;
   L.nnWin = nd.nnWin;
   L.nnLoss = nd.nnLoss;
+  L.nnWeight = nd.nnWeight;
   L.lastSvbDelta = nd.lastSvbDelta;
   L.lastSvbWeight = nd.lastSvbWeight;
   L.visits0 = nd.visits;
@@ -676,11 +680,14 @@ KC_D LevelOut computeLevel(const GV& v, const GameDev& s, PathLevel<NI>& L, cons
     if(ww > 0.001f)
       utility = utility + (sp.svbFactor * dd) / ww;
   }
-  winLossSum = winLossSum + wl;
-  utilitySum = utilitySum + utility;
-  utilitySqSum = utilitySqSum + utility * utility;
-  weightSqSum = weightSqSum + 1.0f;
-  weightSum = weightSum + 1.0f;
+  // the node's own evaluation at its weight (searchupdatehelpers.cpp:291-300; 1 with
+  // uncertainty weighting off)
+  const float selfW = L.nnWeight;
+  winLossSum = winLossSum + wl * selfW;
+  utilitySum = utilitySum + utility * selfW;
+  utilitySqSum = utilitySqSum + (utility * utility) * selfW;
+  weightSqSum = weightSqSum + selfW * selfW;
+  weightSum = weightSum + selfW;
   out.st.winLossAvg = winLossSum / weightSum;
   out.st.utilityAvg = utilitySum / weightSum;
   out.st.utilitySqAvg = utilitySqSum / weightSum;
@@ -1177,6 +1184,7 @@ struct NNCache {
   uint64_t* key;
   float* pol;
   float* val;
+  float* err;
   uint32_t* tag;
 };
 // The cache of net `net`; without MATCH the single one, whatever `net`.
@@ -1184,9 +1192,9 @@ template <bool MATCH>
 KC_D NNCache cacheOf(const SearchDev& d, int net) {
   if constexpr(MATCH) {
     if(net != 0)
-      return NNCache{d.cKey1, d.cPol1, d.cVal1, d.cTag1};
+      return NNCache{d.cKey1, d.cPol1, d.cVal1, d.cErr1, d.cTag1};
   }
-  return NNCache{d.cKey, d.cPol, d.cVal, d.cTag};
+  return NNCache{d.cKey, d.cPol, d.cVal, d.cErr, d.cTag};
 }
 
 template <int NI, bool MATCH = false>
@@ -1203,7 +1211,7 @@ KC_D void cacheLookup(const GV& v, GameDev& s, bool fused) {
     const int pos = v.lane + 64 * j;
     pv[j] = pos < P ? cp[pos] : 0.0f;
   }
-  const float cw = c.val[2 * (size_t)slot], cl = c.val[2 * (size_t)slot + 1];
+  const float cw = c.val[2 * (size_t)slot], cl = c.val[2 * (size_t)slot + 1], ce = c.err[slot];
   const uint32_t tag = fused ? c.tag[slot] : 0u;
   s.cSlot = (int32_t)slot;
   if(tag != 0u) {
@@ -1216,6 +1224,7 @@ KC_D void cacheLookup(const GV& v, GameDev& s, bool fused) {
     s.leafKind = LEAF_CACHED;
     s.cHitWin = cw;
     s.cHitLoss = cl;
+    s.cHitErr = ce;
     float* pol = v.pol(s.leafNode);
 #pragma unroll
     for(int j = 0; j < NI; j++) {
@@ -1409,9 +1418,10 @@ __global__ void __launch_bounds__(64) kResolve(const SearchDev* __restrict__ dp,
 template <int NI>
 // The network row is staged in LDS (one coalesced read) and gathered from there in
 // the symmetric frame; pv returns each lane's policy values for buildOrder.
-// `stage` (>= P+4 floats) may alias polDst.
+// `stage` (>= P+4 floats) may alias polDst.  stLogit: the row's short-term win/loss error
+// logit out[P+3] (uncertainty weighting; the callers that need no weight drop it).
 KC_D void postprocess(const GV& v, const DBoard& b, int sym, const float* out, float* polDst, float& whiteWin,
-                      float& whiteLoss, float* stage, float (&pv)[NI]) {
+                      float& whiteLoss, float& stLogit, float* stage, float (&pv)[NI]) {
   const DTables& T = v.T;
   const int P = T.P, A = T.A;
   if(T.X != T.Y)
@@ -1457,6 +1467,7 @@ KC_D void postprocess(const GV& v, const DBoard& b, int sym, const float* out, f
     legalCount += __popcll(ballot(legal[j]));
   }
   const float wlg = stage[P], llg = stage[P + 1];
+  stLogit = stage[P + 3];
   waveSync();
   mx = waveMax(mx);
   float e[NI];
@@ -1609,9 +1620,9 @@ KC_D bool initMove(const GV& v, GameDev& s, const float* o, float* scratch /* LD
   const SP& b = v.d.sp;
   const int P = v.d.P, A = v.T.A;
   float* pol = scratch;
-  float w, l;
+  float w, l, st;
   float pv[NI];
-  postprocess<NI>(v, s.root, s.leafSym, o, pol, w, l, scratch, pv);
+  postprocess<NI>(v, s.root, s.leafSym, o, pol, w, l, st, scratch, pv);
   waveSync();
   // candidates in ascending policy position: legal with probability > 0
   int* cpos = reinterpret_cast<int*>(scratch + MAX_P);
@@ -1722,10 +1733,13 @@ __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, in
     sideEval<NI>(v, s, o, scratch);
   } else {
     float* pol = scratch;
-    float w, l;
+    float w, l, st;
     float pv[NI];
-    postprocess<NI>(v, s.root, s.leafSym, o, pol, w, l, scratch, pv);
+    postprocess<NI>(v, s.root, s.leafSym, o, pol, w, l, st, scratch, pv);
     waveSync();
+    // the short-term error is averaged over the sampled symmetries like win / loss
+    // (nninputs.cpp:108-119); the root's weight comes from the average
+    const float err = d.unc.on ? stErrorOf(st) : 0.0f;
     float* acc = v.accPolicy();
     if(s.rootK == 0) {
       for(int p = v.lane; p < P; p += 64) {
@@ -1736,11 +1750,13 @@ __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, in
       s.rawLoss = l;
       s.accWin = 0.0f + w;
       s.accLoss = 0.0f + l;
+      s.accErr = 0.0f + err;
     } else {
       for(int p = v.lane; p < P; p += 64)
         acc[p] = acc[p] + pol[p];
       s.accWin = s.accWin + w;
       s.accLoss = s.accLoss + l;
+      s.accErr = s.accErr + err;
     }
     s.rootK++;
     if(s.rootK == sp.rootSyms) {
@@ -1759,12 +1775,13 @@ __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, in
         Node* r = &v.nodes()[s.rootIdx];
         r->nnWin = s.accWin / fl;
         r->nnLoss = s.accLoss / fl;
+        r->nnWeight = uncWeightOf(d.unc, s.accErr / fl);
         r->flags |= 1;
       }
       waveSync();
       if(fresh) {
         const Node& r = v.nodes()[s.rootIdx];
-        addLeafValue(v, s, s.rootIdx, r.nnWin - r.nnLoss, false, true);
+        addLeafValue(v, s, s.rootIdx, r.nnWin - r.nnLoss, r.nnWeight, false, true);
       }
       DRng rng{s.rngSeed, s.rngCtr};
       noiseAndTemp(v, s, rng, rp, v.rootNoised(), scratch);
@@ -1806,7 +1823,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
     NStats leafSt{0u, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     bool haveLeaf = false;
     if(s.leafKind == LEAF_NN || s.leafKind == LEAF_CACHED) {
-      float w, l;
+      float w, l, err = 0.0f;  // err: the evaluation's short-term error (uncertainty weighting)
       float* pol = v.pol(s.leafNode);
       const unsigned long long ta = SPROF_NOW();
       (void)ta;
@@ -1824,8 +1841,12 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
         }
         w = s.cHitWin;
         l = s.cHitLoss;
+        err = s.cHitErr;
       } else {
-        postprocess<NI>(v, s.leaf, s.leafSym, o, pol, w, l, scratch, pv);
+        float st;
+        postprocess<NI>(v, s.leaf, s.leafSym, o, pol, w, l, st, scratch, pv);
+        if(d.unc.on)
+          err = stErrorOf(st);
         if(d.cacheOn) {
           // kCompact bid this evaluation for the state's cache slot (atomicMax of
           // game + 1 over the round's batch); the highest bidder stores its payload
@@ -1842,6 +1863,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
             if(v.lane == 0) {
               c.val[2 * (size_t)slot] = w;
               c.val[2 * (size_t)slot + 1] = l;
+              c.err[slot] = err;
               c.key[2 * (size_t)slot] = v.nodeKey(s.leafNode)[0];
               c.key[2 * (size_t)slot + 1] = v.nodeKey(s.leafNode)[1];
               if(fused)
@@ -1853,26 +1875,28 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
         }
       }
       firstExpansion<NI>(v, s.leafNode, pv);
+      const float weight = uncWeightOf(d.unc, err);
       if(v.lane == 0) {
         Node* n = &v.nodes()[s.leafNode];
         n->nnWin = w;
         n->nnLoss = l;
+        n->nnWeight = weight;
         n->flags |= 1;
       }
       waveSync();
       const unsigned long long tb = SPROF_NOW();
       (void)tb;
-      leafSt = addLeafValue(v, s, s.leafNode, w - l, false, true);
+      leafSt = addLeafValue(v, s, s.leafNode, w - l, weight, false, true);
       haveLeaf = true;
       tPost = tb - ta;
       tLeaf = SPROF_NOW() - tb;
     } else if(s.leafKind == LEAF_TERMINAL) {
       float val = s.leaf.winner == 2 ? 1.0f : (s.leaf.winner == 1 ? -1.0f : 0.0f);
-      leafSt = addLeafValue(v, s, s.leafNode, val, true, false);
+      leafSt = addLeafValue(v, s, s.leafNode, val, uncTerminalWeight(d.unc), true, false);
       haveLeaf = true;
     } else if(s.leafKind == LEAF_NOCHILD) {
       const Node& n = v.nodes()[s.leafNode];
-      leafSt = addLeafValue(v, s, s.leafNode, n.nnWin - n.nnLoss, false, false);
+      leafSt = addLeafValue(v, s, s.leafNode, n.nnWin - n.nnLoss, n.nnWeight, false, false);
       haveLeaf = true;
     }
     const unsigned long long tp0 = SPROF_NOW();
@@ -2734,9 +2758,9 @@ KC_D bool maybeFork(const GV& v, GameDev& s, DRng& rng, uint16_t* legal /* LDS [
 template <int NI>
 KC_D void forkEval(const GV& v, GameDev& s, const float* o, float* scratch) {
   ForkRec* f = v.d.fork + v.g;
-  float w, l;
+  float w, l, st;
   float pv[NI];
-  postprocess<NI>(v, s.leaf, s.leafSym, o, scratch, w, l, scratch, pv);
+  postprocess<NI>(v, s.leaf, s.leafSym, o, scratch, w, l, st, scratch, pv);
   const float wr = 0.5f * (w - l + 1.0f);
   const int pla = f->board.pla;
   const int next = f->next;
@@ -3114,9 +3138,9 @@ KC_D void recordTreePositions(const GV& v, const SP& sp, const GameDev& s, DRng&
 // forking move (no ban); the result joins the queue; then the next side position.
 template <int NI>
 KC_D void sideEval(const GV& v, GameDev& s, const float* o, float* scratch /* LDS [3*MAX_P] */) {
-  float w, l;
+  float w, l, st;
   float pv[NI];
-  postprocess<NI>(v, s.leaf, s.leafSym, o, scratch, w, l, scratch, pv);
+  postprocess<NI>(v, s.leaf, s.leafSym, o, scratch, w, l, st, scratch, pv);
   waveSync();
   DRng rng{s.rngSeed, s.rngCtr};
   // candidates compact in place over the policy (candidate i <= its position)
@@ -3943,7 +3967,8 @@ __global__ void kGameTree(const SearchDev* __restrict__ dp, int g, int maxNodes,
     o[18] = (uint32_t)((uint64_t)sd >> 32);
     o[19] = (uint32_t)(uint64_t)sw;
     o[20] = (uint32_t)((uint64_t)sw >> 32);
-    o[21] = 0;
+    // the node's own evaluation weight with uncertainty weighting on (off: 0, as before)
+    o[21] = d.unc.on ? f2u(x.nnWeight) : 0u;
     o[22] = 0;
     const NodeEdges E{d.edges + ((size_t)g * d.cap + idx) * INLINE_EDGES,
                       d.edgePool + ((size_t)g * 2 + d.games[g].edgeSel) * d.edgePoolCap + x.edgeBase};

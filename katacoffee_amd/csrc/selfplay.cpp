@@ -100,6 +100,20 @@ static T* devAlloc(std::vector<void*>& owned, size_t count, bool zero = true) {
 
 // The settings match play rejects (DESIGN.md "Match play"): each side searches with its own
 // net from a cleared tree, and no training rows are made.
+Unc toUnc(const coffee_uncertainty_params& p) {
+  // setup.cpp:539-562 ranges; !(a <= x && x <= b) also rejects NaN
+  auto in = [](float x, float lo, float hi) { return x >= lo && x <= hi; };
+  if(p.use_uncertainty != 0 && p.use_uncertainty != 1)
+    throw std::invalid_argument("use_uncertainty must be 0 or 1");
+  if(!in(p.uncertainty_coeff, 1e-4f, 1.0f))
+    throw std::invalid_argument("uncertainty_coeff must be in [1e-4, 1]");
+  if(!in(p.uncertainty_exponent, 0.0f, 2.0f))
+    throw std::invalid_argument("uncertainty_exponent must be in [0, 2]");
+  if(!in(p.uncertainty_max_weight, 1.0f, 100.0f))
+    throw std::invalid_argument("uncertainty_max_weight must be in [1, 100]");
+  return Unc{p.use_uncertainty, p.uncertainty_coeff, p.uncertainty_exponent, p.uncertainty_max_weight};
+}
+
 void validateMatchConfig(const coffee_match_config& c) {
   if(c.x < 2 || c.y < 2 || c.x > MAX_LEN || c.y > MAX_LEN)
     throw std::invalid_argument("board size must be 2..10 x 2..10");
@@ -389,11 +403,13 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* cons
     d.cKey = devAlloc<uint64_t>(owned_, entries * 2);  // zero key: never a state
     d.cPol = devAlloc<float>(owned_, entries * P, false);
     d.cVal = devAlloc<float>(owned_, entries * 2, false);
+    d.cErr = devAlloc<float>(owned_, entries, false);
     d.cTag = devAlloc<uint32_t>(owned_, entries);
     if(matchPaths) {  // net 1's own cache
       d.cKey1 = devAlloc<uint64_t>(owned_, entries * 2);
       d.cPol1 = devAlloc<float>(owned_, entries * P, false);
       d.cVal1 = devAlloc<float>(owned_, entries * 2, false);
+      d.cErr1 = devAlloc<float>(owned_, entries, false);
       d.cTag1 = devAlloc<uint32_t>(owned_, entries);
     }
   }
@@ -403,6 +419,11 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* cons
     d.nnCount1 = devAlloc<int32_t>(owned_, 1);
     d.nnPeak = devAlloc<int32_t>(owned_, 2);
     d.nnNetEvals = devAlloc<unsigned long long>(owned_, 2);
+  }
+  {
+    coffee_uncertainty_params u;
+    coffee_uncertainty_params_default(&u);
+    d.unc = toUnc(u);  // off
   }
   d.cClear = devAlloc<uint32_t>(owned_, G);
   d.pendList = devAlloc<int32_t>(owned_, G, false);
@@ -560,6 +581,18 @@ void SelfplayEngine::step(int rounds, hipStream_t st) {
       commitReset_ = true;  // the next kSelect zeroes the count (no separate memset)
     }
   }
+}
+
+void SelfplayEngine::setUncertainty(const coffee_uncertainty_params& p) {
+  const Unc u = toUnc(p);
+  // a tree must never mix the two rules: only before the first round, and in analysis before
+  // the first query (a step loads the queued queries, also one of zero rounds)
+  if(rounds_ > 0 || aSubmitted_ > 0)
+    throw std::invalid_argument(hd_.analysisMode ? "set_uncertainty: only before the first query and round"
+                                                 : "set_uncertainty: only before the engine's first round");
+  hd_.unc = u;
+  // nothing runs yet (the constructor synchronised its initialisation): a plain copy
+  KC_HIP(hipMemcpy(&dd_->unc, &hd_.unc, sizeof(Unc), hipMemcpyHostToDevice));
 }
 
 void SelfplayEngine::forwardNet(int n, const int32_t* count, const int32_t* idx, hipStream_t st, hipEvent_t a,

@@ -12,6 +12,9 @@
 namespace kc {
 
 SP toSP(const coffee_search_params& p);
+// Checks the ranges (throws std::invalid_argument naming the setting; NaN is out of range)
+// and converts.
+Unc toUnc(const coffee_uncertainty_params& p);
 // Checks a match config without touching the device (throws std::invalid_argument naming
 // the offending setting): geometry, and the settings match play rejects because they keep
 // a tree across moves or exist only to make training rows.
@@ -33,6 +36,10 @@ class SelfplayEngine {
   ~SelfplayEngine();
   void step(int rounds, hipStream_t st);
   void sync();
+  // Uncertainty weighting of the evaluations, for every net of the engine.  Only before the
+  // first round (analysis: and the first query); throws std::invalid_argument afterwards or
+  // for out-of-range values, without touching the device.
+  void setUncertainty(const coffee_uncertainty_params& p);
   void stats(coffee_selfplay_stats& out);
   void matchStats(coffee_match_stats& out);
   // Analysis mode: queries into the device ring on the engine stream (returns how many fit),

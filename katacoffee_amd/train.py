@@ -17,7 +17,10 @@ replacement:
   back into ``katago selfplay -models-dir`` (hot reload) or ``coffee_nn_create``;
 * ``losses`` / ``train_step``: policy cross-entropy against the normalised visit
   target, value cross-entropy against the final outcome (draws split evenly between
-  the two logits, matching the engine's two-way softmax of the value head).
+  the two logits, matching the engine's two-way softmax of the value head);
+* ``st_error_loss``: the reference's loss for the short-term value error head (misc[1]),
+  which drives the search's uncertainty weighting; added by ``train_step`` when its
+  ``st_error_weight`` is not 0.
 
 Nothing here runs on the self-play hot path; it is plain PyTorch (any device).
 """
@@ -260,22 +263,52 @@ def rows_to_batch(rows, X, Y, device="cpu"):
     win, loss = gt[:, 0], gt[:, 1]
     draw = np.clip(1.0 - win - loss, 0.0, 1.0)
     vt = np.stack([win + 0.5 * draw, loss + 0.5 * draw], axis=1).astype(np.float32)
+    # the shortest-horizon TD value target, win minus loss of the row's player to move (kRows:
+    # now-factor 1 / (1 + 0.016 A), globalTargets[6:8]); the short-term error head's target
+    v_short = (gt[:, 6] - gt[:, 7]).astype(np.float32)
     return dict(binp=binp, glob=glob, policy=torch.from_numpy(pol).to(device),
-                policy_weight=torch.from_numpy(pw).to(device), value=torch.from_numpy(vt).to(device))
+                policy_weight=torch.from_numpy(pw).to(device), value=torch.from_numpy(vt).to(device),
+                v_short=torch.from_numpy(v_short).to(device))
 
 
-def losses(net, batch):
-    policy, value, _ = net(batch["binp"], batch["glob"])
+def _policy_value_losses(policy, value, batch):
     pl = -(batch["policy"] * F.log_softmax(policy, dim=1)).sum(dim=1)
     pl = (pl * batch["policy_weight"]).sum() / batch["policy_weight"].sum().clamp(min=1.0)
     vl = -(batch["value"] * F.log_softmax(value, dim=1)).sum(dim=1).mean()
     return pl, vl
 
 
-def train_step(net, opt, batch, value_weight=1.0):
+def losses(net, batch):
+    policy, value, _ = net(batch["binp"], batch["glob"])
+    return _policy_value_losses(policy, value, batch)
+
+
+def st_error_loss(value, misc, v_short):
+    """The short-term value error head's loss (metrics_pytorch.py:236-243, model_pytorch.py:75,
+    :1746): misc[:, 1] predicts, as 0.25 * softplus(0.5 x)^2, the squared difference between the
+    value head's own win - loss (detached: the term trains the error head only) and the row's
+    shortest-horizon TD target; Huber with delta 0.4, times 2.  The engine's short-term error
+    (coffee_uncertainty_weight) is the prediction's square root.  The CFNN has no TD value
+    heads, so the value head itself stands in for the reference's third TD head: the search
+    weights that head's output, so its error is the quantity to predict."""
+    probs = torch.softmax(value, dim=1)
+    v_pred = (probs[:, 0] - probs[:, 1]).detach()
+    pred = 0.25 * torch.square(F.softplus(0.5 * misc[:, 1]))
+    target = torch.square(v_pred - v_short) + 1.0e-8
+    return 2.0 * F.huber_loss(pred, target, reduction="mean", delta=0.4)
+
+
+def train_step(net, opt, batch, value_weight=1.0, st_error_weight=0.0):
+    """One optimiser step; returns the policy and value losses.  st_error_weight != 0 adds
+    st_error_loss times that weight (0: the term is not computed, the step is unchanged)."""
     opt.zero_grad()
-    pl, vl = losses(net, batch)
-    total = pl + value_weight * vl
+    if st_error_weight != 0.0:
+        policy, value, misc = net(batch["binp"], batch["glob"])
+        pl, vl = _policy_value_losses(policy, value, batch)
+        total = pl + value_weight * vl + st_error_weight * st_error_loss(value, misc, batch["v_short"])
+    else:
+        pl, vl = losses(net, batch)
+        total = pl + value_weight * vl
     total.backward()
     opt.step()
     return pl.item(), vl.item()

@@ -62,6 +62,8 @@ def main():
     ap.add_argument("--step", type=int, default=100, help="rounds between submissions and drains")
     ap.add_argument("--precision", default="default")
     ap.add_argument("--cache-log2", type=int, default=21)
+    ap.add_argument("--uncertainty", action="store_true",
+                    help="uncertainty weighting on (set_uncertainty(use_uncertainty=1), default values) in both engines")
     a = ap.parse_args()
     search = kc.default_analysis_params(max_visits=a.visits)
     pool = openings(8192, 8, 5)
@@ -71,6 +73,7 @@ def main():
         common = dict(seed=7, commit_interval=16, nn_cache_log2=a.cache_log2, nn_precision=a.precision)
         an = kc.Analysis(X, Y, W, num_slots=a.slots, model_path=path, search=search, query_capacity=4 * a.slots,
                          **common)
+        an.set_uncertainty(use_uncertainty=int(a.uncertainty))
         next_id = [0]
 
         def feed():
@@ -103,6 +106,7 @@ def main():
         over = {k: getattr(search, k) for k, _ in kc.SearchParams._fields_ if k != "max_visits"}
         sp = kc.Selfplay(X, Y, W, num_games=a.slots, model_path=path, max_visits=a.visits, start_stagger=a.visits,
                          **common, **over)
+        sp.set_uncertainty(use_uncertainty=int(a.uncertainty))
         sp.step(a.warmup)
         sp.sync()
         sp.drain_rows()
@@ -120,7 +124,7 @@ def main():
         t_sp = sum(ssecs)
     print(json.dumps({
         "arch": a.arch, "geometry": [X, Y, W], "slots": a.slots, "visits": a.visits, "precision": a.precision,
-        "rounds_per_window": a.rounds, "windows": a.repeats,
+        "rounds_per_window": a.rounds, "windows": a.repeats, "uncertainty": bool(a.uncertainty),
         "analysis": {"positions_per_s": round((s1["queries_finished"] - s0["queries_finished"]) / t_an, 1),
                      "playouts_per_s": round((s1["playouts"] - s0["playouts"]) / t_an, 0),
                      "us_per_round": round(1e6 * t_an / (a.rounds * a.repeats), 2),

@@ -50,6 +50,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--precision", default="default")
     ap.add_argument("--cache-log2", type=int, default=21)
+    ap.add_argument("--uncertainty", action="store_true",
+                    help="uncertainty weighting on (set_uncertainty(use_uncertainty=1), default values) in both engines")
     a = ap.parse_args()
     X, Y, W = 5, 5, 4
     search = kc.default_match_params(max_visits=a.visits)
@@ -61,10 +63,12 @@ def main():
         common = dict(num_games=a.games, seed=7, commit_interval=16, nn_cache_log2=a.cache_log2,
                       nn_precision=a.precision, start_stagger=a.visits)
         m = kc.Match(X, Y, W, baseline_path=paths[0], candidate_path=paths[1], search=search, **common)
+        m.set_uncertainty(use_uncertainty=int(a.uncertainty))
         msecs, mgames, mst = timed(m, a.rounds, a.warmup, a.repeats, m.drain_games)
         m.close()
         over.pop("max_visits")
         s = kc.Selfplay(X, Y, W, model_path=paths[0], max_visits=a.visits, **common, **over)
+        s.set_uncertainty(use_uncertainty=int(a.uncertainty))
 
         def drain_sp():
             s.drain_rows()
@@ -75,7 +79,7 @@ def main():
     med_m, med_s = statistics.median(msecs), statistics.median(ssecs)
     print(json.dumps({
         "arch": a.arch, "geometry": [X, Y, W], "games": a.games, "visits": a.visits, "precision": a.precision,
-        "rounds_per_window": a.rounds, "windows": a.repeats,
+        "rounds_per_window": a.rounds, "windows": a.repeats, "uncertainty": bool(a.uncertainty),
         "match": {"games_per_s": round(mgames, 2), "rounds_per_s": round(a.rounds / med_m, 1),
                   "us_per_round": round(1e6 * med_m / a.rounds, 2), "window_s": [round(x, 4) for x in msecs],
                   "nn_evals": mst["nn_evals"], "nn_batch_peak": mst["nn_batch_peak"],
