@@ -21,6 +21,7 @@ Tolerances (on policy/value/misc logits):
                      (b6c96 random init); deeper nets are printed (fp16 operand noise
                      grows with depth, ~1e-3 of the largest logit for b18c384nbt)
 """
+import importlib.util
 import os
 
 import numpy as np
@@ -30,6 +31,11 @@ import katacoffee_amd as kc
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("symmetry", os.path.join(REPO, "tests", "helpers", "symmetry.py"))
+symmetry = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(symmetry)
 
 
 def _pack_u64(planes):
@@ -166,30 +172,6 @@ def test_selfplay_runs_on_layered_network(models, arch, X, Y, W):
     assert st["moves"] > 0 and st["nn_evals"] > 0
 
 
-def _symmetry_maps(X, Y, W):
-    """symCell[s][c], symDir[s][d] derived from the oracle's (reference-pinned) V1
-    encoder, independently of the device tables: a lone own stone at c lights plane 1
-    at symCell[s][c]; a last move in direction d lights plane 3 + symDir[s][d]."""
-    A = X * Y
-    cells = np.zeros((8 * A, A), np.uint8)
-    cells[np.arange(8 * A), np.tile(np.arange(A), 8)] = 1
-    hc = np.full((8 * A, 5), -1, np.int8)
-    hd = np.full((8 * A, 5), 4, np.int8)
-    sym = np.repeat(np.arange(8), A).astype(np.int32)
-    binp, _ = oracle.encode_batch(X, Y, W, cells, hc, hd, np.ones(8 * A, np.uint8), sym)
-    sym_cell = binp[:, 1, :].argmax(axis=1).reshape(8, A)
-    cells = np.zeros((32, A), np.uint8)
-    cells[:, A // 2] = 2
-    hc = np.full((32, 5), -1, np.int8)
-    hd = np.full((32, 5), 4, np.int8)
-    hc[:, 0] = A // 2
-    hd[:, 0] = np.tile(np.arange(4), 8)
-    sym = np.repeat(np.arange(8), 4).astype(np.int32)
-    binp, _ = oracle.encode_batch(X, Y, W, cells, hc, hd, np.ones(32, np.uint8), sym)
-    sym_dir = binp[:, 3:7, :].sum(axis=2).argmax(axis=1).reshape(8, 4)
-    return sym_cell, sym_dir
-
-
 @pytest.mark.parametrize("arch,X,Y,W,precision", [("b6c96", 5, 5, 4, "accurate"), ("b6c96", 5, 5, 4, "fast"),
                                                   ("b10c128", 7, 7, 5, "accurate")])
 def test_forward_canonical_frame_vs_oracle(models, arch, X, Y, W, precision):
@@ -221,11 +203,7 @@ def test_forward_canonical_frame_vs_oracle(models, arch, X, Y, W, precision):
     raw = net.forward(packed)
     np.testing.assert_array_equal(net.forward_canonical(packed, np.zeros(n, np.int32)), raw)
     net.close()
-    sym_cell, sym_dir = _symmetry_maps(X, Y, W)
-    src = np.zeros((8, P), np.int64)
-    for s in range(8):
-        for d in range(4):
-            src[s, d * A:(d + 1) * A] = sym_dir[s, d] * A + sym_cell[s]
+    src = symmetry.canonical_source(X, Y, W)
     # the device's own symmetric-frame output, mapped back: exact
     expect = raw.copy()
     expect[:, :P] = np.take_along_axis(raw[:, :P], src[sym], axis=1)
