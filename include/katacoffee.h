@@ -572,6 +572,73 @@ int coffee_selfplay_set_uncertainty(coffee_selfplay* h, const coffee_uncertainty
 int coffee_match_set_uncertainty(coffee_match* h, const coffee_uncertainty_params* p);
 int coffee_analysis_set_uncertainty(coffee_analysis* h, const coffee_uncertainty_params* p);
 
+/* ---- start positions (the reference's startPoses, play.cpp:186-248, :400-448) ----
+ * A share of the games starts from a sample of a table of positions instead of the empty
+ * board.  A sample is a move list from the empty board (policy positions dir * A + cell, black
+ * first, 0 <= num_moves < A) with a weight; its unnormalised probability is
+ * exp(-num_moves * turn_weight_lambda) * weight (generateCumProbs).  The host turns the
+ * probabilities (in double) into 64-bit fixed-point cumulative thresholds: nondecreasing,
+ * cum[n-1] = 2^64 - 1, a zero-weight sample repeats its predecessor's threshold and is never
+ * picked.  A game's draws, on its own stream after the two game-hash draws and before the
+ * policy-init draw: u = uni(); if u < prob, r = next() and the sample is the first i with
+ * r < cum[i] (r = 2^64 - 1: the last sample with positive weight).  Without a table or with
+ * prob 0 no draw is made and nothing changes.  A game from a sample has the sample's moves as
+ * unsearched turns (no rows), mode 4 in its rows' gt[55] (MODE_SGFPOS), gt[53] = its start
+ * turn, and its policy-init move count drawn with start_policy_init_area_prop in place of
+ * policy_init_area_prop (0: no draw).  The sample's trainingWeight, hint positions and
+ * asymmetric playouts of the reference are not built. */
+typedef struct coffee_start_position {
+  float weight;
+  int32_t num_moves;
+  uint16_t moves[COFFEE_ANALYSIS_MAX_MOVES];
+} coffee_start_position;
+typedef struct coffee_start_positions_params {
+  float prob;                          /* 0, range [0, 1]     startPosesProb */
+  float turn_weight_lambda;            /* 0, range [-10, 10]  startPosesTurnWeightLambda */
+  float start_policy_init_area_prop;   /* 0, range [0, 1]     startPosesPolicyInitAreaProp */
+} coffee_start_positions_params;
+void coffee_start_positions_params_default(coffee_start_positions_params* p);
+/* Replays n samples (host) with the device rules at the geometry, one wave per sample:
+ * status_out[i] (host) is COFFEE_ANALYSIS_OK, _ILLEGAL_MOVE (info_out[i] = index of the move;
+ * also a move >= 4 * x * y, and a num_moves outside 0..A-1 with info -1), _GAME_OVER (info =
+ * winner) or _NO_LEGAL_MOVE. */
+int coffee_start_positions_check(int x, int y, int win_len, int n, const coffee_start_position* samples,
+                                 int32_t* status_out, int32_t* info_out);
+/* The thresholds of n samples on the host (no device is touched).  COFFEE_EINVAL for a
+ * negative or non-finite weight, a table whose weights are all zero, n < 1 or a lambda
+ * outside its range. */
+int coffee_start_positions_thresholds(const coffee_start_position* samples, int n, float turn_weight_lambda,
+                                      uint64_t* cum_out);
+/* The pick alone: the sample of raw draw r under thresholds cum[n] (n >= 1).  This and
+ * coffee_start_position_draws below are for a caller that has to verify or reproduce a run:
+ * a game's draw r is not an input of coffee_start_position_pick, so the rule at r = 0,
+ * r = cum[i] and r = 2^64 - 1, and how many draws a game start consumed, can be observed only
+ * through them (like coffee_uncertainty_weight, the kernels' own code on the host). */
+int coffee_start_position_index(const uint64_t* cum, int n, uint64_t r, int* index);
+/* The sample game game_num of global slot global_slot (slot_base + slot) takes under engine
+ * seed `seed`, or -1 for the empty board, on the host with the kernels' own code: the seed
+ * formula, the two hash draws, then the draws above.  cum NULL or n 0: no table. */
+int coffee_start_position_pick(uint64_t seed, uint32_t global_slot, uint32_t game_num, float prob,
+                               const uint64_t* cum, int n, int* index);
+/* The same, and the stream's counter after the pick's draws: 2 (the hash draws) when the
+ * feature is off, 3 after a u >= prob, 4 after a pick. */
+int coffee_start_position_draws(uint64_t seed, uint32_t global_slot, uint32_t game_num, float prob,
+                                const uint64_t* cum, int n, int* index, uint64_t* rng_counter);
+/* Sets the table of an engine: checks the parameters and every sample (the check kernel above),
+ * builds the thresholds and uploads both in order with the engine stream (the call waits for
+ * the stream's work, checks on it, then copies).  A bad sample or parameter
+ * returns COFFEE_EINVAL (the first bad sample's index in coffee_last_error()) and leaves the
+ * engine as it was.  Allowed between steps at any time; applies to every game that starts
+ * afterwards; before the engine's first round it also restarts every slot's first game, so
+ * those see the table.  n = 0 or prob = 0 turns the feature off. */
+int coffee_selfplay_set_start_positions(coffee_selfplay* h, const coffee_start_position* samples, int n,
+                                        const coffee_start_positions_params* params);
+int coffee_match_set_start_positions(coffee_match* h, const coffee_start_position* samples, int n,
+                                     const coffee_start_positions_params* params);
+/* Games started from the table so far. */
+int coffee_selfplay_start_position_games(coffee_selfplay* h, uint64_t* games);
+int coffee_match_start_position_games(coffee_match* h, uint64_t* games);
+
 /* Writes n rows (HOST arrays, drain_rows layout) as a training .npz in the reference's
  * format (TrainingWriteBuffers::writeToZipFile trainingwrite.cpp:566-587): members
  * binaryInputNCHWPacked, globalInputNC, policyTargetsNCMove, globalTargetsNC,

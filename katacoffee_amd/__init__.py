@@ -129,6 +129,11 @@ class UncertaintyParams(ctypes.Structure):
                 ("uncertainty_exponent", ctypes.c_float), ("uncertainty_max_weight", ctypes.c_float)]
 
 
+class StartPositionsParams(ctypes.Structure):
+    _fields_ = [("prob", ctypes.c_float), ("turn_weight_lambda", ctypes.c_float),
+                ("start_policy_init_area_prop", ctypes.c_float)]
+
+
 ANALYSIS_MAX_MOVES = 100
 ANALYSIS_MAX_PV = 16
 ANALYSIS_OK, ANALYSIS_ILLEGAL_MOVE, ANALYSIS_GAME_OVER, ANALYSIS_NO_LEGAL_MOVE = 0, 1, 2, 3
@@ -170,6 +175,10 @@ ANALYSIS_MOVE = np.dtype([("move", np.int32), ("edge_visits", np.uint32), ("visi
                           ("prior", np.float32), ("lcb", np.float32), ("radius", np.float32),
                           ("play_selection_value", np.float32), ("order", np.int32), ("pv_len", np.int32),
                           ("pv", np.uint16, (ANALYSIS_MAX_PV,))], align=True)
+# coffee_start_position
+START_POSITION = np.dtype([("weight", np.float32), ("num_moves", np.int32),
+                           ("moves", np.uint16, (ANALYSIS_MAX_MOVES,))], align=True)
+assert START_POSITION.itemsize == 208
 assert ANALYSIS_QUERY.itemsize == 232 and ANALYSIS_RESULT.itemsize == 56 and ANALYSIS_MOVE.itemsize == 80
 
 
@@ -196,6 +205,9 @@ EXPORTS = [
     "coffee_analysis_root_policy",
     "coffee_uncertainty_params_default", "coffee_uncertainty_weight", "coffee_selfplay_set_uncertainty",
     "coffee_match_set_uncertainty", "coffee_analysis_set_uncertainty",
+    "coffee_start_positions_params_default", "coffee_start_positions_check", "coffee_start_positions_thresholds",
+    "coffee_start_position_pick", "coffee_start_position_draws", "coffee_start_position_index", "coffee_selfplay_set_start_positions",
+    "coffee_match_set_start_positions", "coffee_selfplay_start_position_games", "coffee_match_start_position_games",
 ]
 
 
@@ -292,6 +304,20 @@ def lib():
         L.coffee_selfplay_set_uncertainty.argtypes = [c_p, c_p]
         L.coffee_match_set_uncertainty.argtypes = [c_p, c_p]
         L.coffee_analysis_set_uncertainty.argtypes = [c_p, c_p]
+        if hasattr(L, "coffee_start_positions_check"):  # (absent in earlier builds run as A/B references)
+            L.coffee_start_positions_params_default.argtypes = [c_p]
+            L.coffee_start_positions_params_default.restype = None
+            L.coffee_start_positions_check.argtypes = [c_i, c_i, c_i, c_i, c_p, c_p, c_p]
+            L.coffee_start_positions_thresholds.argtypes = [c_p, c_i, ctypes.c_float, c_p]
+            L.coffee_start_position_index.argtypes = [c_p, c_i, c_u64, c_p]
+            L.coffee_start_position_pick.argtypes = [c_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_p, c_i,
+                                                     c_p]
+            L.coffee_start_position_draws.argtypes = [c_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_p, c_i,
+                                                      c_p, c_p]
+            L.coffee_selfplay_set_start_positions.argtypes = [c_p, c_p, c_i, c_p]
+            L.coffee_match_set_start_positions.argtypes = [c_p, c_p, c_i, c_p]
+            L.coffee_selfplay_start_position_games.argtypes = [c_p, c_p]
+            L.coffee_match_start_position_games.argtypes = [c_p, c_p]
         _lib = L
     return _lib
 
@@ -359,6 +385,83 @@ def uncertainty_weight(logit, params=None, **over):
     check(lib().coffee_uncertainty_weight(ctypes.byref(p), ctypes.c_float(float(logit)), ctypes.byref(err),
                                           ctypes.byref(w)))
     return np.float32(err.value), np.float32(w.value)
+
+
+def start_positions(positions):
+    """Start positions as a START_POSITION array.  positions: such an array, or a list whose
+    entries are move lists (policy positions dir * A + cell from the empty board, black first;
+    weight 1), (moves, weight) pairs or dicts with `moves` and optionally `weight`."""
+    if isinstance(positions, np.ndarray) and positions.dtype == START_POSITION:
+        return np.ascontiguousarray(positions)
+    out = np.zeros(len(positions), START_POSITION)
+    for i, q in enumerate(positions):
+        if isinstance(q, dict):
+            moves, w = q.get("moves", ()), q.get("weight", 1.0)
+        elif len(q) == 2 and not np.isscalar(q[0]) and np.isscalar(q[1]):
+            moves, w = q
+        else:
+            moves, w = q, 1.0
+        moves = list(moves)
+        if len(moves) > ANALYSIS_MAX_MOVES:
+            raise CoffeeError("start position %d: more than %d moves" % (i, ANALYSIS_MAX_MOVES))
+        if any(m < 0 or m > 0xFFFF for m in moves):
+            raise CoffeeError("start position %d: a move is not a policy position" % i)
+        out[i]["weight"] = w
+        out[i]["num_moves"] = len(moves)
+        out[i]["moves"][:len(moves)] = moves
+    return out
+
+
+def start_positions_check(X, Y, W, positions):
+    """(status, info) int32 arrays of coffee_start_positions_check: every sample replayed with
+    the device rules (ANALYSIS_OK / _ILLEGAL_MOVE + move index / _GAME_OVER + winner /
+    _NO_LEGAL_MOVE)."""
+    _torch_cuda()
+    t = start_positions(positions)
+    status = np.zeros(len(t), np.int32)
+    info = np.zeros(len(t), np.int32)
+    check(lib().coffee_start_positions_check(X, Y, W, len(t), _ptr(t), _ptr(status), _ptr(info)))
+    return status, info
+
+
+def start_positions_thresholds(positions, turn_weight_lambda=0.0):
+    """The table's 64-bit cumulative thresholds (coffee_start_positions_thresholds, host only)."""
+    t = start_positions(positions)
+    cum = np.zeros(len(t), np.uint64)
+    check(lib().coffee_start_positions_thresholds(_ptr(t) if len(t) else None, len(t),
+                                                  ctypes.c_float(turn_weight_lambda), _ptr(cum) if len(t) else None))
+    return cum
+
+
+def start_position_index(cum, r):
+    """The sample of raw 64-bit draw r under thresholds cum (coffee_start_position_index)."""
+    c = np.ascontiguousarray(cum, np.uint64)
+    idx = ctypes.c_int()
+    check(lib().coffee_start_position_index(_ptr(c) if len(c) else None, len(c), r, ctypes.byref(idx)))
+    return idx.value
+
+
+def start_position_pick(seed, global_slot, game_num, prob, cum, with_counter=False):
+    """The sample game `game_num` of global slot `global_slot` takes, or -1 for the empty
+    board (coffee_start_position_pick: the kernels' own code on the host).  cum: the thresholds
+    or None (no table).  with_counter: (index, the stream's counter after the draws)."""
+    idx = ctypes.c_int()
+    ctr = ctypes.c_uint64()
+    n = 0 if cum is None else len(cum)
+    c = None if n == 0 else _ptr(np.ascontiguousarray(cum, np.uint64))
+    if with_counter:
+        check(lib().coffee_start_position_draws(seed, global_slot, game_num, ctypes.c_float(prob), c, n,
+                                                ctypes.byref(idx), ctypes.byref(ctr)))
+        return idx.value, ctr.value
+    check(lib().coffee_start_position_pick(seed, global_slot, game_num, ctypes.c_float(prob), c, n,
+                                           ctypes.byref(idx)))
+    return idx.value
+
+
+def _set_start_positions(fn, h, positions, prob, turn_weight_lambda, start_policy_init_area_prop):
+    t = start_positions(positions if positions is not None else [])
+    p = StartPositionsParams(prob, turn_weight_lambda, start_policy_init_area_prop)
+    check(fn(h, _ptr(t) if len(t) else None, len(t), ctypes.byref(p)))
 
 
 def analysis_queries(queries):
@@ -644,6 +747,22 @@ class Selfplay:
         p = _uncertainty_params(params, over)
         check(lib().coffee_selfplay_set_uncertainty(self.h, ctypes.byref(p)))
 
+    def set_start_positions(self, positions, prob, turn_weight_lambda=0.0, start_policy_init_area_prop=0.0):
+        """Start positions (coffee_selfplay_set_start_positions): games that start from now on
+        begin with probability `prob` from a sample of `positions` (see start_positions()),
+        weighted by weight * exp(-moves * turn_weight_lambda).  Between steps at any time; before
+        the first round the slots' first games are started again.  A sample the device rules
+        reject, or an out-of-range value: CoffeeError, engine untouched.  No positions or
+        prob 0: off."""
+        _set_start_positions(lib().coffee_selfplay_set_start_positions, self.h, positions, prob,
+                             turn_weight_lambda, start_policy_init_area_prop)
+
+    def start_position_games(self):
+        """Games started from the start-position table so far."""
+        n = ctypes.c_uint64()
+        check(lib().coffee_selfplay_start_position_games(self.h, ctypes.byref(n)))
+        return n.value
+
     def sync(self):
         check(lib().coffee_selfplay_sync(self.h))
 
@@ -812,6 +931,18 @@ class Match:
         the first round (one setting serves both nets); afterwards, or for out-of-range values, CoffeeError."""
         p = _uncertainty_params(params, over)
         check(lib().coffee_match_set_uncertainty(self.h, ctypes.byref(p)))
+
+    def set_start_positions(self, positions, prob, turn_weight_lambda=0.0, start_policy_init_area_prop=0.0):
+        """Start positions (coffee_match_set_start_positions), as Selfplay.set_start_positions:
+        opening variety that depends on neither net's policy."""
+        _set_start_positions(lib().coffee_match_set_start_positions, self.h, positions, prob,
+                             turn_weight_lambda, start_policy_init_area_prop)
+
+    def start_position_games(self):
+        """Games started from the start-position table so far."""
+        n = ctypes.c_uint64()
+        check(lib().coffee_match_start_position_games(self.h, ctypes.byref(n)))
+        return n.value
 
     def sync(self):
         check(lib().coffee_match_sync(self.h))

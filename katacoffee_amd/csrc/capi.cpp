@@ -763,6 +763,86 @@ int coffee_analysis_set_uncertainty(coffee_analysis* h, const coffee_uncertainty
   });
 }
 
+// ---- start positions (startpos.h: the thresholds and the pick the kernels run) ----
+
+void coffee_start_positions_params_default(coffee_start_positions_params* p) {
+  if(!p)
+    return;
+  p->prob = 0.0f;
+  p->turn_weight_lambda = 0.0f;
+  p->start_policy_init_area_prop = 0.0f;
+}
+
+int coffee_start_positions_check(int x, int y, int win_len, int n, const coffee_start_position* samples,
+                                 int32_t* status_out, int32_t* info_out) {
+  return guarded([&] {
+    checkGeom(x, y, win_len);
+    checkStartPositions(x, y, win_len, n, samples, status_out, info_out);
+  });
+}
+
+int coffee_start_positions_thresholds(const coffee_start_position* samples, int n, float turn_weight_lambda,
+                                      uint64_t* cum_out) {
+  return guarded([&] { startPosThresholdsOf(samples, n, turn_weight_lambda, cum_out); });
+}
+
+int coffee_start_position_index(const uint64_t* cum, int n, uint64_t r, int* index) {
+  return guarded([&] {
+    need(cum && index && n >= 1, "start positions: NULL argument or n < 1");
+    *index = startPosIndex(cum, n, r);
+  });
+}
+
+int coffee_start_position_draws(uint64_t seed, uint32_t global_slot, uint32_t game_num, float prob,
+                                const uint64_t* cum, int n, int* index, uint64_t* rng_counter) {
+  return guarded([&] {
+    need(index != nullptr, "NULL argument");
+    need(n >= 0 && prob >= 0.0f && prob <= 1.0f, "start positions: n >= 0 and prob in [0, 1]");
+    // startGame's stream: the seed, the two game-hash draws, then the start-position draws
+    DRng rng{gameStreamSeed(seed, global_slot, game_num), 0};
+    rng.next();
+    rng.next();
+    *index = startPosDraw(rng, prob, cum, n);
+    if(rng_counter)
+      *rng_counter = rng.ctr;
+  });
+}
+
+int coffee_start_position_pick(uint64_t seed, uint32_t global_slot, uint32_t game_num, float prob,
+                               const uint64_t* cum, int n, int* index) {
+  return coffee_start_position_draws(seed, global_slot, game_num, prob, cum, n, index, nullptr);
+}
+
+int coffee_selfplay_set_start_positions(coffee_selfplay* h, const coffee_start_position* samples, int n,
+                                        const coffee_start_positions_params* params) {
+  return guarded([&] {
+    need(h && h->eng && params, "NULL argument");
+    h->eng->setStartPositions(samples, n, *params);
+  });
+}
+
+int coffee_match_set_start_positions(coffee_match* h, const coffee_start_position* samples, int n,
+                                     const coffee_start_positions_params* params) {
+  return guarded([&] {
+    need(h && h->eng && params, "NULL argument");
+    h->eng->setStartPositions(samples, n, *params);
+  });
+}
+
+int coffee_selfplay_start_position_games(coffee_selfplay* h, uint64_t* games) {
+  return guarded([&] {
+    need(h && h->eng && games, "NULL argument");
+    *games = h->eng->startPositionGames();
+  });
+}
+
+int coffee_match_start_position_games(coffee_match* h, uint64_t* games) {
+  return guarded([&] {
+    need(h && h->eng && games, "NULL argument");
+    *games = h->eng->startPositionGames();
+  });
+}
+
 int coffee_debug_cdf_table(int x, int y, int win_len, float* out) {
   return guarded([&] {
     need(out != nullptr, "NULL argument");

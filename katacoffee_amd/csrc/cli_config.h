@@ -38,6 +38,14 @@ inline bool readConfig(const std::string& path, std::map<std::string, std::strin
   return true;
 }
 
+// startPosesFromSgfDir / startPosesFile / startPosesLoadProb and the library's parameters
+// (startPosesProb, startPosesTurnWeightLambda, startPosesPolicyInitAreaProp): cli_startpos.h
+struct StartPosSettings {
+  std::string sgfDirs, file;
+  float loadProb = 1.0f;
+  coffee_start_positions_params params = {0.0f, 0.0f, 0.0f};
+};
+
 struct Settings {
   int x = 5, y = 5, winLen = 4, games = 4096, gpus = 1, maxRowsPerFile = 10000;
   int servers = 1;  // numNNServerThreadsPerModel: self-play engines (own stream, batch, cache) over all GPUs
@@ -53,6 +61,7 @@ struct Settings {
   // off) by the command before applyConfig; off unless the config turns it on, for all three
   // commands (the reference's loader defaults it on for analysis, GTP and match, setup.cpp:539-562)
   coffee_uncertainty_params unc;
+  StartPosSettings startPos;  // off unless startPosesProb > 0 and a source is named
 };
 
 inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& s) {
@@ -196,6 +205,18 @@ inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& 
   getfIn("uncertaintyCoeff", s.unc.uncertainty_coeff, 0.0001f, 1.0f);
   getfIn("uncertaintyExponent", s.unc.uncertainty_exponent, 0.0f, 2.0f);
   getfIn("uncertaintyMaxWeight", s.unc.uncertainty_max_weight, 1.0f, 100.0f);
+  // start positions (play.cpp:186-196 getters: the same ranges)
+  auto gets = [&](const char* k, std::string& v) {
+    auto f = kv.find(k);
+    if(f != kv.end())
+      v = f->second;
+  };
+  gets("startPosesFromSgfDir", s.startPos.sgfDirs);
+  gets("startPosesFile", s.startPos.file);
+  getfIn("startPosesProb", s.startPos.params.prob, 0.0f, 1.0f);
+  getfIn("startPosesLoadProb", s.startPos.loadProb, 0.0f, 1.0f);
+  getfIn("startPosesTurnWeightLambda", s.startPos.params.turn_weight_lambda, -10.0f, 10.0f);
+  getfIn("startPosesPolicyInitAreaProp", s.startPos.params.start_policy_init_area_prop, 0.0f, 1.0f);
 }
 
 }  // namespace kccli

@@ -36,6 +36,7 @@
 
 #include "../../include/katacoffee.h"
 #include "cli_config.h"
+#include "cli_startpos.h"
 #include "cli_util.h"
 
 using namespace kccli;
@@ -68,7 +69,8 @@ void moveModel(const std::string& file, const std::string& toDir) {
 }
 
 // One gating: true when a candidate was found (and judged), false when there was none.
-bool gateOnce(const Settings& s, int gamesPerGating, const Dirs& d, bool autoReject, uint64_t seed) {
+bool gateOnce(const Settings& s, int gamesPerGating, const Dirs& d, bool autoReject, uint64_t seed,
+              const std::vector<coffee_start_position>& startPos) {
   time_t candTime = 0, baseTime = 0;
   const std::string cand = newestModelOrEmpty(d.test, &candTime);
   if(cand.empty())
@@ -108,6 +110,10 @@ bool gateOnce(const Settings& s, int gamesPerGating, const Dirs& d, bool autoRej
   if(s.unc.use_uncertainty)
     logf("gatekeeper: uncertainty weighting on for both nets: coeff %g, exponent %g, max weight %g",
          s.unc.uncertainty_coeff, s.unc.uncertainty_exponent, s.unc.uncertainty_max_weight);
+  // opening variety that depends on neither net's policy (cli_startpos.h)
+  if(!startPos.empty())
+    must(coffee_match_set_start_positions(h, startPos.data(), (int)startPos.size(), &s.startPos.params),
+         "set start positions");
   logf("gatekeeper: %s (candidate) against %s, %d games on %d slots, %dx%d win %d, %d visits", candName.c_str(),
        baseName.c_str(), N, G, s.x, s.y, s.winLen, s.sp.max_visits);
   const std::string sgfDir = d.sgf + "/" + candName;
@@ -256,10 +262,33 @@ int gatekeeperMain(int argc, char** argv) {
   }
   std::signal(SIGINT, onQuit);
   std::signal(SIGTERM, onQuit);
-  std::random_device rd;
+  // the run seed: `seed` in the config (or -override-config) repeats a run -- the gatings' engine
+  // seeds and the startPosesLoadProb draws all come from it; unset, it is drawn and logged
+  uint64_t runSeed = 0;
+  {
+    std::random_device rd;
+    runSeed = rd() ^ ((uint64_t)rd() << 32);
+    auto it = kv.find("seed");
+    if(it != kv.end()) {
+      char* end = nullptr;
+      runSeed = strtoull(it->second.c_str(), &end, 10);
+      if(it->second.empty() || *end != 0)
+        fail("config key seed: bad value '" + it->second + "'");
+    }
+  }
+  logf("gatekeeper: run seed %llu", (unsigned long long)runSeed);
+  std::mt19937_64 seeds(runSeed);
+  // the run's start positions: loaded and checked once, the same table for every gating
+  std::vector<coffee_start_position> startPos;
+  try {
+    startPos = prepareStartPositions(s.startPos, s.x, s.y, s.winLen, runSeed, "gatekeeper",
+                                     [](const std::string& m) { logf("%s", m.c_str()); });
+  } catch(const std::exception& e) {
+    fail(e.what());
+  }
   while(!gQuit) {
-    const uint64_t seed = rd() ^ ((uint64_t)rd() << 32);
-    if(!gateOnce(s, gamesPerGating, d, autoReject, seed)) {
+    const uint64_t seed = seeds();
+    if(!gateOnce(s, gamesPerGating, d, autoReject, seed, startPos)) {
       if(quitIfNone)
         break;
       for(int i = 0; i < 20 && !gQuit; i++)

@@ -41,6 +41,7 @@
 
 #include "../../include/katacoffee.h"
 #include "cli_config.h"
+#include "cli_startpos.h"
 #include "cli_util.h"
 
 using namespace kccli;
@@ -170,6 +171,8 @@ struct SgfSink {
 };
 
 static std::atomic<int64_t> gGamesDone(0);
+// The run's start positions (cli_startpos.h): loaded and checked once, set on every engine
+static std::vector<coffee_start_position> gStartPos;
 
 // One self-play engine: `share` of GPU `gpu`'s games from slot `slot` on (the
 // reference's NN server thread with its game threads).  Engines on one device run
@@ -206,6 +209,10 @@ static void runGpu(int gpu, int server, int perGpu, int slot, int share, const S
   if(s.unc.use_uncertainty)
     logf("gpu %d.%d: uncertainty weighting on: coeff %g, exponent %g, max weight %g", gpu, server,
          s.unc.uncertainty_coeff, s.unc.uncertainty_exponent, s.unc.uncertainty_max_weight);
+  // the table stays across hot reloads (set_model does not touch it)
+  if(!gStartPos.empty())
+    check(coffee_selfplay_set_start_positions(h, gStartPos.data(), (int)gStartPos.size(), &s.startPos.params),
+          "set start positions");
   std::mt19937_64 fileRng(s.seed ^ (0x9E3779B97F4A7C15ULL * (gpu + 1)) ^ ((uint64_t)server << 48));
   auto dirsFor = [&](const std::string& m, std::string& tdata, std::string& sgfs) {
     tdata = outDir + "/" + modelNameOf(m) + "/tdata";
@@ -361,6 +368,17 @@ int main(int argc, char** argv) {
   }
   s.maxGamesTotal = maxGames;
   s.seed = std::random_device{}() ^ ((uint64_t)std::random_device{}() << 32);
+  {
+    // `seed` in the config (or -override-config) repeats a run: the engines' game streams and the
+    // startPosesLoadProb draws come from it; unset, it is drawn here and logged below
+    auto it = kv.find("seed");
+    if(it != kv.end()) {
+      char* end = nullptr;
+      s.seed = strtoull(it->second.c_str(), &end, 10);
+      if(it->second.empty() || *end != 0)
+        die("config key seed: bad value '" + it->second + "'");
+    }
+  }
   mkdirs(outDir);
   char lname[64];
   time_t now = time(nullptr);
@@ -390,6 +408,13 @@ int main(int argc, char** argv) {
     die("numGpus must be in 1.." + std::to_string(ndev));
   logf("selfplay: model %s, %dx%d win %d, %d games/GPU x %d GPUs, %d visits", model.c_str(), s.x, s.y, s.winLen,
        s.games, s.gpus, s.sp.max_visits);
+  logf("selfplay: run seed %llu", (unsigned long long)s.seed);
+  try {
+    gStartPos = prepareStartPositions(s.startPos, s.x, s.y, s.winLen, s.seed, "selfplay",
+                                      [](const std::string& m) { logf("%s", m.c_str()); });
+  } catch(const std::exception& e) {
+    die(e.what());
+  }
   // numNNServerThreadsPerModel engines spread over the GPUs: floor / ceil per GPU so the
   // total is exactly the configured count (the reference gives each server thread its
   // GPU, gpuToUseThreadN); every GPU runs at least one.  A GPU's games split evenly

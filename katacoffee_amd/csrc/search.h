@@ -23,6 +23,7 @@
 #pragma once
 #include "../../include/katacoffee.h"
 #include "kc_common.h"
+#include "startpos.h"
 #include "uncertainty.h"
 
 namespace kc {
@@ -244,7 +245,11 @@ struct GameDev {
   int32_t rootIdx, liveCount, freeTop, pathLen;
   int32_t gameNum, numTurns, svbSel, err;
   int32_t edgeSel, edgeTop;       // current edge-pool buffer, its first free slot
-  int32_t edgePeak, pad0;         // edge-pool high-water mark (stats)
+  int32_t edgePeak;               // edge-pool high-water mark (stats)
+  // start positions: sample + 1 whose moves kStartPosTurns still has to write into the turn
+  // records (0: none) -- kCommit starts the slot's next game before kRows has read the
+  // finished game's records
+  int32_t spPending;
   float accWin, accLoss, rawWin, rawLoss;
 };
 
@@ -375,6 +380,16 @@ struct SearchDev {
   DPtr<unsigned long long> aCtr;        // [AC_N] running counts (AnalysisCounter)
   DPtr<AnalysisSlot> aSlot;             // [G]
   unsigned long long aSubmitted;        // host copy only: queries submitted so far (launchCommit hands it on)
+  // start positions (coffee_*_set_start_positions): a game starts from sample
+  // startPosDraw picks with probability spProb (spN == 0 or spProb == 0: off, no draw).  Every
+  // sample passed kStartPosCheck before the table was set.
+  DPtr<const coffee_start_position> spTable;  // [spN]
+  DPtr<const uint64_t> spCum;                 // [spN] cumulative thresholds (startpos.h)
+  int32_t spN;
+  float spProb;
+  float spInitAreaProp;                       // startPosesPolicyInitAreaProp
+  int32_t spPad;
+  DPtr<unsigned long long> spGames;           // games started from the table so far
 };
 
 // Match play: the candidate (net 1) plays black (player 1) in game number n of global
@@ -418,5 +433,11 @@ void launchGameTree(const SearchDev* dd, int slot, int maxNodes, uint32_t* nodes
                     int32_t* count, hipStream_t st);
 // Dynamic LDS bytes the commit kernel needs for node_cap `cap`.
 size_t commitLdsBytes(int cap);
+// Replays n start-position samples (device array) with the device rules at geometry T (device
+// tables; P = 4A), one wave per sample: status[i] a COFFEE_ANALYSIS_* code, info[i] its detail.
+// (weak: selfplay.cpp and capi.cpp also link host-only, without search.hip's kernels; the
+// caller then reports the missing kernel as an error instead of failing to link)
+void launchStartPosCheck(const DTables* T, int P, const coffee_start_position* samples, int n, int32_t* status,
+                         int32_t* info, hipStream_t st) __attribute__((weak));
 
 }  // namespace kc

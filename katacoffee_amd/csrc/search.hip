@@ -1604,7 +1604,7 @@ KC_D void firstExpansion(const GV& v, int ni, const float (&pv)[NI]) {
 KC_D bool setMoveLimits(const GV& v, GameDev& s, DRng& rng, float lastWL);
 template <bool MATCH = false>
 KC_D void finishGameRecord(const GV& v, const GameDev& s, DRng& rng, float* scratch);
-KC_D void startGame(const GV& v, GameDev& s);
+KC_D void startGame(const GV& v, GameDev& s, bool deferTurns = false);
 template <int NI>
 KC_D void forkEval(const GV& v, GameDev& s, const float* o, float* scratch);
 template <int NI>
@@ -2607,8 +2607,101 @@ KC_D bool setMoveLimits(const GV& v, GameDev& s, DRng& rng, float lastWL) {
   return clear;
 }
 
-KC_D void startGame(const GV& v, GameDev& s) {
-  s.rngSeed = mix64(v.d.seed ^ mix64(((uint64_t)(v.d.slotBase + v.g) << 32) | (uint32_t)s.gameNum));
+// The replay of start-position sample `sp` from the empty board into b (every lane holds the
+// same b; the rules are wave-wide).  Every decision is taken on readfirstlane values, so the
+// branches stay scalar and every lane stays active for playMoveWave's ballot.
+// CHECK: each move is tested before it is played and the index of the first bad one returned
+// (-1: none); without it the moves are only clamped into the policy range -- the table passed
+// the check before it was set -- and the replay stops should the game end.  nm: the moves
+// played.  Nothing indexes past the sample or the tables whatever the sample holds.
+template <bool W1, bool CHECK>
+KC_D int replayStartPos(const DTables& T, DBoard& b, const coffee_start_position* sp, int A, int P, int& nm) {
+  const int want = __builtin_amdgcn_readfirstlane((int)sp->num_moves);
+  const int n = min(max(want, 0), min(A - 1, COFFEE_ANALYSIS_MAX_MOVES));
+  boardInit(T, b);
+  waveSync();
+  int bad = -1, t = 0;
+  for(; t < n; t++) {
+    int mv = __builtin_amdgcn_readfirstlane((int)sp->moves[t]);
+    if(__builtin_amdgcn_readfirstlane(b.finished) != 0) {
+      bad = t;
+      break;
+    }
+    if(CHECK) {
+      bool ok = mv < P;
+      if(ok)
+        ok = __builtin_amdgcn_readfirstlane((int)isLegal<W1>(T, b, mv % A, mv / A)) != 0;
+      if(!ok) {
+        bad = t;
+        break;
+      }
+    } else {
+      mv = min(mv, P - 1);
+    }
+    playMoveWave<W1>(T, b, mv % A, mv / A);
+    waveSync();
+  }
+  nm = t;
+  return bad;
+}
+
+// One wave per sample of a start-position table: the replay with the device rules, status and
+// info as analysisRefill reports a query it cannot search.
+template <int NI>
+__global__ void __launch_bounds__(64) kStartPosCheck(const DTables* __restrict__ Tp,
+                                                     const coffee_start_position* __restrict__ samples, int n,
+                                                     int32_t* __restrict__ status, int32_t* __restrict__ info) {
+  const DTables& T = *Tp;
+  const int i = blockIdx.x;
+  if(i >= n)
+    return;
+  __shared__ DBoard b;
+  const coffee_start_position* sp = samples + i;
+  const int A = T.A, P = T.P;
+  const int want = __builtin_amdgcn_readfirstlane((int)sp->num_moves);
+  int nm = 0;
+  const int bad = replayStartPos<W1_OF<NI>, true>(T, b, sp, A, P, nm);
+  waveSync();
+  int st = COFFEE_ANALYSIS_OK, inf = 0;
+  if(want < 0 || want >= A || want > COFFEE_ANALYSIS_MAX_MOVES) {
+    st = COFFEE_ANALYSIS_ILLEGAL_MOVE;
+    inf = -1;
+  } else if(bad >= 0) {
+    st = COFFEE_ANALYSIS_ILLEGAL_MOVE;
+    inf = bad;
+  } else if(b.finished != 0) {
+    if(b.winner == 0 && b.turn < A) {
+      st = COFFEE_ANALYSIS_NO_LEGAL_MOVE;
+    } else {
+      st = COFFEE_ANALYSIS_GAME_OVER;
+      inf = b.winner;
+    }
+  }
+  if(laneId() == 0) {
+    status[i] = st;
+    info[i] = inf;
+  }
+}
+
+// The moves of start-position sample sp as unsearched turn records of game v.g (as
+// startForkGame and analysisRefill write theirs); nm: the moves the replay played.
+KC_D void writeStartPosTurns(const GV& v, const coffee_start_position* sp, int nm) {
+  TurnRec* tr = v.turns();
+  for(int t = v.lane; t < nm; t += 64) {
+    const int mv = min((int)sp->moves[t], v.T.P - 1);
+    TurnRec rec;
+    memset(&rec, 0, sizeof(rec));
+    rec.gen = (uint8_t)*v.d.modelGen;
+    rec.cell = (int8_t)(mv % v.T.A);
+    rec.dir = (int8_t)(mv / v.T.A);
+    tr[t] = rec;
+  }
+}
+
+// deferTurns (kCommit): a start position's turn records are left to kStartPosTurns, which
+// runs after kRows -- that kernel still reads the finished game's records from the same array.
+KC_D void startGame(const GV& v, GameDev& s, bool deferTurns) {
+  s.rngSeed = gameStreamSeed(v.d.seed, (uint32_t)(v.d.slotBase + v.g), (uint32_t)s.gameNum);
   s.rngCtr = 0;
   s.startGen = *v.d.modelGen;
   boardInit(v.T, s.root);
@@ -2625,12 +2718,40 @@ KC_D void startGame(const GV& v, GameDev& s) {
   // opening moves sampled from the raw policy (nextExponential rand.h:299-305)
   s.startTurn = 0;
   s.initLeft = 0;
+  s.spPending = 0;
   const SP& b = v.d.sp;
-  if(b.initPolicy && b.initAreaProp > 0.0f) {
+  float areaProp = b.initAreaProp;
+  // start positions (startpos.h; play.cpp:400-448): with a table set, a share of the games
+  // starts from a sampled move list, replayed here as unsearched turns; policy init stays
+  // allowed with its own area proportion (allowPolicyInit, play.cpp:1228-1231).  No table or
+  // probability 0: no draw
+  const int spN = __builtin_amdgcn_readfirstlane(v.d.spN);
+  if(spN > 0) {
+    const uint64_t* cum = v.d.spCum;
+    const int pick = __builtin_amdgcn_readfirstlane(startPosDraw(rng, v.d.spProb, cum, spN));
+    if(pick >= 0) {
+      const coffee_start_position* sp = v.d.spTable + min(pick, spN - 1);
+      int nm = 0;
+      replayStartPos<false, false>(v.T, s.root, sp, v.T.A, v.T.P, nm);
+      nm = __builtin_amdgcn_readfirstlane(nm);
+      if(deferTurns)
+        s.spPending = min(pick, spN - 1) + 1;
+      else
+        writeStartPosTurns(v, sp, nm);
+      s.numTurns = nm;
+      s.startTurn = nm;
+      s.gameMode = 4;  // FinishedGameData::MODE_SGFPOS
+      areaProp = v.d.spInitAreaProp;
+      if(v.lane == 0)
+        atomicAdd((unsigned long long*)v.d.spGames, 1ull);
+      waveSync();
+    }
+  }
+  if(b.initPolicy && areaProp > 0.0f) {
     float u = rng.uni();
     while(u <= 0.0f)
       u = rng.uni();
-    s.initLeft = (int)floorf(-dlog(u) * ((float)v.T.A * b.initAreaProp));
+    s.initLeft = (int)floorf(-dlog(u) * ((float)v.T.A * areaProp));
   }
   if(s.initLeft > 0) {
     s.phase = PH_INIT;
@@ -2863,7 +2984,10 @@ KC_D void startSideSearch(const GV& v, GameDev& s) {
 
 // After a game's rows: its side positions are searched, then the fork decision and
 // the slot's next game (play.cpp:1576-1662, selfplay gameLoop :2008).
-KC_D void afterGame(const GV& v, GameDev& s, DRng& rng, uint16_t* scratch) {
+// inCommit: called from kCommit, whose kRows has yet to read the finished game's turn records,
+// so a start position's records are left to kStartPosTurns (startGame's deferTurns); sideEval
+// runs in a round kernel with no kRows pending and lets startGame write them.
+KC_D void afterGame(const GV& v, GameDev& s, DRng& rng, uint16_t* scratch, bool inCommit) {
   if(s.sideNext < s.sideCount) {
     startSideSearch(v, s);
     s.rngCtr = rng.ctr;
@@ -2871,7 +2995,7 @@ KC_D void afterGame(const GV& v, GameDev& s, DRng& rng, uint16_t* scratch) {
   }
   s.sideMode = 0;
   if(!maybeFork(v, s, rng, scratch))
-    startGame(v, s);
+    startGame(v, s, inCommit);
   else
     s.rngCtr = rng.ctr;
 }
@@ -3152,7 +3276,7 @@ KC_D void sideEval(const GV& v, GameDev& s, const float* o, float* scratch /* LD
     pushSide(v, s, b3);
   }
   s.sideNext++;
-  afterGame(v, s, rng, reinterpret_cast<uint16_t*>(scratch + MAX_P));
+  afterGame(v, s, rng, reinterpret_cast<uint16_t*>(scratch + MAX_P), false);
   waveSync();
 }
 
@@ -3511,7 +3635,7 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
     s.gamesFinished++;
     s.gameNum++;
     s.sideNext = 0;
-    afterGame(v, s, rng, reinterpret_cast<uint16_t*>(lds));
+    afterGame(v, s, rng, reinterpret_cast<uint16_t*>(lds), true);
     waveSync();
     storeGame(v, s);
     return;
@@ -3567,7 +3691,7 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
       }
     }
     s.sideNext++;
-    afterGame(v, s, rng, reinterpret_cast<uint16_t*>(posv));
+    afterGame(v, s, rng, reinterpret_cast<uint16_t*>(posv), true);
     waveSync();
     storeGame(v, s);
     return;
@@ -3610,7 +3734,7 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
     s.gameNum++;
     s.sideNext = 0;
     waveSync();
-    afterGame(v, s, rng, reinterpret_cast<uint16_t*>(posv));
+    afterGame(v, s, rng, reinterpret_cast<uint16_t*>(posv), true);
     SPROF_ADD(20, t4 - t3);
     SPROF_ADD(21, SPROF_NOW() - t4);
     SPROF_ADD(23, 1);
@@ -3632,6 +3756,30 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
   SPROF_ADD(16, 1);
   SPROF_ADD(17, SPROF_NOW() - t0);
   SPROF_FLUSH();
+}
+
+// After kCommit (and kRows) with a start-position table set: the committed games whose next
+// game kCommit started from a sample get the sample's moves as turn records now that kRows
+// has read the finished game's.  One wave per commit-list entry.
+__global__ void __launch_bounds__(64) kStartPosTurns(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp) {
+  const SearchDev& d = *dp;
+  if((int)blockIdx.x >= *d.commitCount)
+    return;
+  const int g = d.commitList[blockIdx.x];
+  GameDev* gs = d.games + g;
+  const int pend = __builtin_amdgcn_readfirstlane(gs->spPending);
+  const int spN = d.spN;
+  if(pend <= 0 || spN <= 0)
+    return;
+  GV v(d, *Tp, g);
+  const coffee_start_position* sp = d.spTable + min(pend - 1, spN - 1);
+  // the replay played numTurns moves when the game started in this launch's kCommit; nothing
+  // has run for the game since
+  const int nm = min(max(__builtin_amdgcn_readfirstlane(gs->numTurns), 0), min(d.A - 1, COFFEE_ANALYSIS_MAX_MOVES));
+  writeStartPosTurns(v, sp, nm);
+  waveSync();
+  if(v.lane == 0)
+    gs->spPending = 0;
 }
 
 // kCompact: the list of games whose row the network evaluates this round, at most
@@ -4343,6 +4491,20 @@ void launchStageRows(const SearchDev& d, const SearchDev* dd, uint8_t* dst, unsi
   KC_HIP(hipGetLastError());
 }
 
+void launchStartPosCheck(const DTables* T, int P, const coffee_start_position* samples, int n, int32_t* status,
+                         int32_t* info, hipStream_t st) {
+  if(n <= 0)
+    return;
+  const int ni = laneItems(P);
+  if(ni == 2)
+    hipLaunchKernelGGL((kStartPosCheck<2>), dim3(n), dim3(64), 0, st, T, samples, n, status, info);
+  else if(ni == 4)
+    hipLaunchKernelGGL((kStartPosCheck<4>), dim3(n), dim3(64), 0, st, T, samples, n, status, info);
+  else
+    hipLaunchKernelGGL((kStartPosCheck<7>), dim3(n), dim3(64), 0, st, T, samples, n, status, info);
+  KC_HIP(hipGetLastError());
+}
+
 void launchSelfplayInit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
   hipLaunchKernelGGL(kInit, dim3(d.G), dim3(64), 0, st, dd, d.T);
   KC_HIP(hipGetLastError());
@@ -4473,6 +4635,10 @@ void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
       default: hipLaunchKernelGGL((kCommit<7, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
     }
     KC_HIP(hipGetLastError());
+    if(d.spN > 0) {
+      hipLaunchKernelGGL(kStartPosTurns, dim3(d.G), dim3(64), 0, st, dd, d.T);
+      KC_HIP(hipGetLastError());
+    }
     return;
   }
   switch(laneItems(d.P)) {
@@ -4483,6 +4649,10 @@ void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
   KC_HIP(hipGetLastError());
   hipLaunchKernelGGL(kRows, dim3(d.G), dim3(64 * ROWS_WAVES), 0, st, dd, d.T);
   KC_HIP(hipGetLastError());
+  if(d.spN > 0) {  // a start-position table is set: the new games' turn records, after kRows
+    hipLaunchKernelGGL(kStartPosTurns, dim3(d.G), dim3(64), 0, st, dd, d.T);
+    KC_HIP(hipGetLastError());
+  }
 }
 
 void launchGameTree(const SearchDev* dd, int slot, int maxNodes, uint32_t* nodesOut, uint32_t* edgesOut,

@@ -450,6 +450,7 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* cons
   d.gRec = devAlloc<GameRec>(owned_, (size_t)d.gCap, false);
   d.gCount = devAlloc<unsigned long long>(owned_, 1);
   d.gDropped = devAlloc<unsigned long long>(owned_, 1);
+  d.spGames = devAlloc<unsigned long long>(owned_, 1);  // no start-position table: spN 0
   dd_ = devAlloc<SearchDev>(owned_, 1);
   KC_HIP(hipMemcpy(dd_, &d, sizeof(SearchDev), hipMemcpyHostToDevice));
   KC_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
@@ -473,6 +474,10 @@ SelfplayEngine::~SelfplayEngine() {
     n.nn.reset();
   for(void* p : owned_)
     (void)hipFree(p);
+  if(hd_.spTable.p)
+    (void)hipFree(const_cast<coffee_start_position*>(hd_.spTable.p));
+  if(hd_.spCum.p)
+    (void)hipFree(const_cast<uint64_t*>(hd_.spCum.p));
   if(stream_)
     (void)hipStreamDestroy(stream_);
 }
@@ -593,6 +598,151 @@ void SelfplayEngine::setUncertainty(const coffee_uncertainty_params& p) {
   hd_.unc = u;
   // nothing runs yet (the constructor synchronised its initialisation): a plain copy
   KC_HIP(hipMemcpy(&dd_->unc, &hd_.unc, sizeof(Unc), hipMemcpyHostToDevice));
+}
+
+// ---- start positions (startpos.h) ----
+
+void validateStartPosParams(const coffee_start_positions_params& p) {
+  // the reference's getters (play.cpp:190-196, setup / PlaySettings); NaN is out of range
+  auto in = [](float x, float lo, float hi) { return x >= lo && x <= hi; };
+  if(!in(p.prob, 0.0f, 1.0f))
+    throw std::invalid_argument("start positions: prob must be in [0, 1]");
+  if(!in(p.turn_weight_lambda, -10.0f, 10.0f))
+    throw std::invalid_argument("start positions: turn_weight_lambda must be in [-10, 10]");
+  if(!in(p.start_policy_init_area_prop, 0.0f, 1.0f))
+    throw std::invalid_argument("start positions: start_policy_init_area_prop must be in [0, 1]");
+}
+
+void startPosThresholdsOf(const coffee_start_position* samples, int n, float lambda, uint64_t* cum) {
+  if(n < 1 || !samples || !cum)
+    throw std::invalid_argument("start positions: the table needs at least one sample");
+  if(!(lambda >= -10.0f && lambda <= 10.0f))
+    throw std::invalid_argument("start positions: turn_weight_lambda must be in [-10, 10]");
+  std::vector<float> w(n);
+  std::vector<int32_t> t(n);
+  for(int i = 0; i < n; i++) {
+    w[i] = samples[i].weight;
+    t[i] = samples[i].num_moves;
+    if(!(w[i] >= 0.0f) || !std::isfinite(w[i]))
+      throw std::invalid_argument("start position " + std::to_string(i) + ": weight must be finite and >= 0");
+    if(!std::isfinite(std::exp(-(double)t[i] * (double)lambda) * (double)w[i]))
+      throw std::invalid_argument("start position " + std::to_string(i) + ": weight * exp(-num_moves * lambda) is " +
+                                  "not finite (num_moves " + std::to_string(t[i]) + ")");
+  }
+  // what is left for the builder to refuse: no sample with a positive probability, or a sum past double
+  if(!startPosThresholds(w.data(), t.data(), n, (double)lambda, cum))
+    throw std::invalid_argument("start positions: no sample has a positive probability (or their sum is not finite)");
+}
+
+// The check kernel on samples already on the device (st: any stream; synchronised here).
+static void checkStartPosDevice(const DTables* T, int P, const coffee_start_position* dev, int n, int32_t* status,
+                                int32_t* info, hipStream_t st) {
+  std::vector<void*> tmp;
+  struct Free {
+    std::vector<void*>& t;
+    ~Free() {
+      for(void* p : t)
+        (void)hipFree(p);
+    }
+  } guard{tmp};
+  // (weak in search.h: a host-only link of the engine has no kernels; never null in the library)
+  if(!launchStartPosCheck)
+    throw InternalError("start positions: this build has no check kernel");
+  int32_t* ds = devAlloc<int32_t>(tmp, (size_t)n, false);
+  int32_t* di = devAlloc<int32_t>(tmp, (size_t)n, false);
+  KC_HIP(hipMemsetAsync(ds, 0xFF, sizeof(int32_t) * n, st));
+  KC_HIP(hipMemsetAsync(di, 0, sizeof(int32_t) * n, st));
+  launchStartPosCheck(T, P, dev, n, ds, di, st);
+  KC_HIP(hipStreamSynchronize(st));
+  KC_HIP(hipMemcpy(status, ds, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  KC_HIP(hipMemcpy(info, di, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+}
+
+void checkStartPositions(int x, int y, int winLen, int n, const coffee_start_position* samples, int32_t* status,
+                         int32_t* info) {
+  if(n < 0 || (n > 0 && (!samples || !status || !info)))
+    throw std::invalid_argument("start positions: NULL argument or n < 0");
+  if(n == 0)
+    return;
+  const DTables* T = deviceTables(x, y, winLen);
+  coffee_start_position* dev = nullptr;
+  KC_HIP(hipMalloc(&dev, sizeof(coffee_start_position) * (size_t)n));
+  try {
+    KC_HIP(hipMemcpy(dev, samples, sizeof(coffee_start_position) * (size_t)n, hipMemcpyHostToDevice));
+    checkStartPosDevice(T, 4 * x * y, dev, n, status, info, nullptr);
+  } catch(...) {
+    (void)hipFree(dev);
+    throw;
+  }
+  KC_HIP(hipFree(dev));
+}
+
+void SelfplayEngine::setStartPositions(const coffee_start_position* samples, int n,
+                                       const coffee_start_positions_params& p) {
+  if(hd_.analysisMode)
+    throw std::invalid_argument("start positions: not for an analysis engine");
+  validateStartPosParams(p);
+  if(n < 0 || (n > 0 && !samples))
+    throw std::invalid_argument("start positions: NULL table or n < 0");
+  coffee_start_position* table = nullptr;
+  uint64_t* cumDev = nullptr;
+  if(n > 0) {
+    // host part first: weights and thresholds; then the replay of every sample on the device,
+    // into buffers of its own -- the engine's state is untouched until the table is accepted
+    std::vector<uint64_t> cum(n);
+    startPosThresholdsOf(samples, n, p.turn_weight_lambda, cum.data());
+    std::vector<int32_t> status(n), info(n);
+    KC_HIP(hipMalloc(&table, sizeof(coffee_start_position) * (size_t)n));
+    try {
+      // (blocking copies into buffers no kernel reads yet; the check itself runs on the engine stream)
+      KC_HIP(hipMemcpy(table, samples, sizeof(coffee_start_position) * (size_t)n, hipMemcpyHostToDevice));
+      checkStartPosDevice(T_, hd_.P, table, n, status.data(), info.data(), stream_);
+      for(int i = 0; i < n; i++)
+        if(status[i] != COFFEE_ANALYSIS_OK) {
+          static const char* const what[] = {"", "illegal move at index ", "the moves end the game, winner ",
+                                             "no legal move"};
+          std::string m = "start position " + std::to_string(i) + ": " + what[status[i] & 3];
+          if(status[i] != COFFEE_ANALYSIS_NO_LEGAL_MOVE)
+            m += std::to_string(info[i]);
+          throw std::invalid_argument(m);
+        }
+      KC_HIP(hipMalloc(&cumDev, sizeof(uint64_t) * (size_t)n));
+      KC_HIP(hipMemcpy(cumDev, cum.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice));
+    } catch(...) {
+      (void)hipFree(table);
+      (void)hipFree(cumDev);
+      throw;
+    }
+  }
+  sync();  // nothing of the engine runs while the table changes hands
+  coffee_start_position* oldTable = const_cast<coffee_start_position*>(hd_.spTable.p);
+  uint64_t* oldCum = const_cast<uint64_t*>(hd_.spCum.p);
+  hd_.spTable = table;
+  hd_.spCum = cumDev;
+  hd_.spN = n;
+  hd_.spProb = n > 0 ? p.prob : 0.0f;
+  hd_.spInitAreaProp = p.start_policy_init_area_prop;
+  // the start-position fields are the tail of SearchDev; the engine stream is idle (sync above),
+  // so a plain copy is ordered before the next launch on it
+  const size_t off = (size_t)((const char*)&hd_.spTable - (const char*)&hd_);
+  KC_HIP(hipMemcpy((char*)dd_ + off, (const char*)&hd_ + off, sizeof(SearchDev) - off, hipMemcpyHostToDevice));
+  if(rounds_ == 0) {
+    // no round ran yet: every slot's first game starts again, now with the table
+    KC_HIP(hipMemsetAsync(hd_.spGames, 0, sizeof(unsigned long long), stream_));
+    launchSelfplayInit(hd_, dd_, stream_);
+  }
+  KC_HIP(hipStreamSynchronize(stream_));
+  if(oldTable)
+    (void)hipFree(oldTable);
+  if(oldCum)
+    (void)hipFree(oldCum);
+}
+
+uint64_t SelfplayEngine::startPositionGames() {
+  sync();
+  unsigned long long v = 0;
+  KC_HIP(hipMemcpy(&v, hd_.spGames, 8, hipMemcpyDeviceToHost));
+  return v;
 }
 
 void SelfplayEngine::forwardNet(int n, const int32_t* count, const int32_t* idx, hipStream_t st, hipEvent_t a,

@@ -15,6 +15,13 @@ SP toSP(const coffee_search_params& p);
 // Checks the ranges (throws std::invalid_argument naming the setting; NaN is out of range)
 // and converts.
 Unc toUnc(const coffee_uncertainty_params& p);
+// Start positions: the parameters' ranges; the thresholds of a table on the host (startpos.h);
+// the check kernel on a host table at a geometry.  Each throws std::invalid_argument naming
+// the setting or the first bad sample.
+void validateStartPosParams(const coffee_start_positions_params& p);
+void startPosThresholdsOf(const coffee_start_position* samples, int n, float lambda, uint64_t* cum);
+void checkStartPositions(int x, int y, int winLen, int n, const coffee_start_position* samples, int32_t* status,
+                         int32_t* info);
 // Checks a match config without touching the device (throws std::invalid_argument naming
 // the offending setting): geometry, and the settings match play rejects because they keep
 // a tree across moves or exist only to make training rows.
@@ -40,6 +47,12 @@ class SelfplayEngine {
   // first round (analysis: and the first query); throws std::invalid_argument afterwards or
   // for out-of-range values, without touching the device.
   void setUncertainty(const coffee_uncertainty_params& p);
+  // Start positions: checks the parameters and every sample (kStartPosCheck),
+  // builds the thresholds and uploads both once the engine stream is idle; between steps at any time.
+  // Throws std::invalid_argument (naming the first bad sample) with the engine untouched.
+  // Before the first round every slot's first game is started again.  n = 0: off.
+  void setStartPositions(const coffee_start_position* samples, int n, const coffee_start_positions_params& p);
+  uint64_t startPositionGames();  // games started from the table so far
   void stats(coffee_selfplay_stats& out);
   void matchStats(coffee_match_stats& out);
   // Analysis mode: queries into the device ring on the engine stream (returns how many fit),
