@@ -567,10 +567,60 @@ int coffee_uncertainty_weight(const coffee_uncertainty_params* p, float st_error
  * 108-110).  Only before the engine's first round, and for analysis before the first query is
  * submitted: a tree never mixes the two rules.  Afterwards, or for out-of-range or non-finite
  * values, COFFEE_EINVAL without touching the device.  With the setting on, word 21 of each
- * coffee_*_game_tree node holds the f32 bits of the node's own evaluation weight (off: 0). */
+ * coffee_*_game_tree node holds the f32 bits of the node's own evaluation weight (off: 0).
+ * A match engine with per-side settings (coffee_match_create2, per_side) refuses the call:
+ * its sides carry their own, and word 21 follows the side whose search built the tree. */
 int coffee_selfplay_set_uncertainty(coffee_selfplay* h, const coffee_uncertainty_params* p);
 int coffee_match_set_uncertainty(coffee_match* h, const coffee_uncertainty_params* p);
 int coffee_analysis_set_uncertainty(coffee_analysis* h, const coffee_uncertainty_params* p);
+
+/* ---- per-side match settings (the reference's `katago match`, whose search keys
+ *      take a bot suffix, cpp/command/match.cpp) ----
+ * A match engine whose two sides search with their own parameters and uncertainty weighting,
+ * and which may run both sides on one network instance -- the same net with two settings is
+ * how a setting's strength is measured.
+ * Side: side 1 is what coffee_match_config calls the candidate (black in game n of global slot
+ * s iff s + n is even), side 0 the baseline; the game records' candidate colour is side 1's.
+ * per_side = 1: every parameter a search reads -- descent, FPU, cpuct, root symmetries, noise
+ *   and temperature, uncertainty weight, subtree value bias, graph search, the visit limit and
+ *   the move choice at the commit -- is the one of the side that searches.  The game-level
+ *   settings stay one per engine and come from cfg->search: init_games_with_policy,
+ *   policy_init_area_prop, policy_init_area_temperature (a side that differs there is rejected).
+ *   coffee_match_set_uncertainty then returns COFFEE_EINVAL: the sides carry their own.
+ *   With node_cap = 0 the default comes from the larger of the two sides' max_visits.
+ * per_side = 0: cfg->search and coffee_match_set_uncertainty serve both sides; side[] is ignored.
+ * share_net = 1: the two model paths must be equal strings (both NULL counts as equal).  One
+ *   network instance, one launch a round on every taken row, one evaluation cache (its payload
+ *   is the post-processed policy, the values and the raw short-term error, stored whenever
+ *   either side weights by it: an entry serves both sides whichever wrote it, as the
+ *   reference shares one NNEvaluator).  coffee_match_stats then reports 0 in
+ *   nn_evals[1], nn_batch_peak[1], nn_precision[1] and net 1's audit fields.
+ * Rejected with COFFEE_EINVAL before any device call, coffee_last_error() naming the side and
+ * the field: a side's parameters that coffee_match_create would reject as cfg->search, a
+ * side's uncertainty parameters out of range, a differing game-level field, share_net with
+ * unequal model paths, a side's max_visits the node pool cannot serve (node_cap, rounded up
+ * to 64, must be >= max_visits + 4). */
+typedef struct coffee_match_side {
+  coffee_search_params search;
+  coffee_uncertainty_params unc;
+} coffee_match_side;
+typedef struct coffee_match_options {
+  int32_t per_side;   /* 0: cfg->search and coffee_match_set_uncertainty serve both sides */
+  int32_t share_net;  /* 1: one network instance, one launch per round, one cache */
+  coffee_match_side side[2];
+} coffee_match_options;
+/* opts NULL: coffee_match_create. */
+int coffee_match_create2(const coffee_match_config* cfg, const coffee_match_options* opts, coffee_match** out);
+/* Elo of a result from one side's view (host, doubles), N = wins + draws + losses:
+ *   score  p = (W + D/2) / N
+ *   se       = sqrt(((W (1-p)^2 + D (0.5-p)^2 + L p^2) / N) / N)
+ *   elo(x)   = -400 log10(1/x - 1)
+ *   *elo = elo(p), *elo_lo / *elo_hi = elo(p -/+ 1.96 se), -inf / +inf where the argument
+ *   leaves (0, 1)
+ *   *los     = 0.5 erfc(-(W - L) / sqrt(2 (W + L))), 0.5 when W + L = 0
+ * Any output may be NULL.  COFFEE_EINVAL for a negative count or N = 0. */
+int coffee_match_elo(int64_t wins, int64_t draws, int64_t losses, double* score, double* elo, double* elo_lo,
+                     double* elo_hi, double* los);
 
 /* ---- start positions (the reference's startPoses, play.cpp:186-248, :400-448) ----
  * A share of the games starts from a sample of a table of positions instead of the empty

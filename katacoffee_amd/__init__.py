@@ -129,6 +129,16 @@ class UncertaintyParams(ctypes.Structure):
                 ("uncertainty_exponent", ctypes.c_float), ("uncertainty_max_weight", ctypes.c_float)]
 
 
+class MatchSide(ctypes.Structure):
+    """coffee_match_side: one side's search parameters and uncertainty weighting."""
+    _fields_ = [("search", SearchParams), ("unc", UncertaintyParams)]
+
+
+class MatchOptions(ctypes.Structure):
+    """coffee_match_options (coffee_match_create2)."""
+    _fields_ = [("per_side", ctypes.c_int32), ("share_net", ctypes.c_int32), ("side", MatchSide * 2)]
+
+
 class StartPositionsParams(ctypes.Structure):
     _fields_ = [("prob", ctypes.c_float), ("turn_weight_lambda", ctypes.c_float),
                 ("start_policy_init_area_prop", ctypes.c_float)]
@@ -208,6 +218,7 @@ EXPORTS = [
     "coffee_start_positions_params_default", "coffee_start_positions_check", "coffee_start_positions_thresholds",
     "coffee_start_position_pick", "coffee_start_position_draws", "coffee_start_position_index", "coffee_selfplay_set_start_positions",
     "coffee_match_set_start_positions", "coffee_selfplay_start_position_games", "coffee_match_start_position_games",
+    "coffee_match_create2", "coffee_match_elo",
 ]
 
 
@@ -318,6 +329,9 @@ def lib():
             L.coffee_match_set_start_positions.argtypes = [c_p, c_p, c_i, c_p]
             L.coffee_selfplay_start_position_games.argtypes = [c_p, c_p]
             L.coffee_match_start_position_games.argtypes = [c_p, c_p]
+        if hasattr(L, "coffee_match_create2"):  # (absent in earlier builds run as A/B references)
+            L.coffee_match_create2.argtypes = [c_p, c_p, c_p]
+            L.coffee_match_elo.argtypes = [ctypes.c_int64] * 3 + [c_p] * 5
         _lib = L
     return _lib
 
@@ -505,6 +519,49 @@ def match_score(header):
     c, b = ctypes.c_double(), ctypes.c_double()
     check(lib().coffee_match_score(_ptr(header), len(header), ctypes.byref(c), ctypes.byref(b)))
     return c.value, b.value
+
+
+def match_elo(wins, draws, losses):
+    """Elo of a result from one side's view (coffee_match_elo; host, doubles): a dict with the
+    score, elo, the 95% interval elo_lo / elo_hi (-inf / inf where it leaves (0, 1)) and los,
+    the likelihood of superiority.  No games: CoffeeError."""
+    out = [ctypes.c_double() for _ in range(5)]
+    check(lib().coffee_match_elo(int(wins), int(draws), int(losses), *[ctypes.byref(o) for o in out]))
+    return dict(zip(["score", "elo", "elo_lo", "elo_hi", "los"], [o.value for o in out]))
+
+
+def _match_side(base, spec, index):
+    """One entry of Match(sides=...) as a MatchSide on top of the engine's search `base`: a dict
+    of SearchParams / UncertaintyParams field overrides, or a (SearchParams, UncertaintyParams)
+    pair (either may be None: the engine's search / uncertainty off)."""
+    side = MatchSide()
+    side.search = SearchParams.from_buffer_copy(base)
+    side.unc = default_uncertainty_params()
+    if isinstance(spec, dict):
+        sfields = {n for n, _ in SearchParams._fields_}
+        ufields = {n for n, _ in UncertaintyParams._fields_}
+        for k, v in spec.items():
+            if k in sfields:
+                setattr(side.search, k, v)
+            elif k in ufields:
+                setattr(side.unc, k, v)
+            else:
+                raise CoffeeError("Match sides[%d]: %r is neither a SearchParams nor an UncertaintyParams field"
+                                  % (index, k))
+    elif isinstance(spec, (tuple, list)) and len(spec) == 2:
+        sp, un = spec
+        if sp is not None:
+            if not isinstance(sp, SearchParams):
+                raise CoffeeError("Match sides[%d]: the pair's first entry must be a SearchParams" % index)
+            side.search = SearchParams.from_buffer_copy(sp)
+        if un is not None:
+            if not isinstance(un, UncertaintyParams):
+                raise CoffeeError("Match sides[%d]: the pair's second entry must be an UncertaintyParams" % index)
+            side.unc = UncertaintyParams.from_buffer_copy(un)
+    else:
+        raise CoffeeError("Match sides[%d]: a dict of field overrides or a (SearchParams, UncertaintyParams) pair"
+                          % index)
+    return side
 
 
 # ---------------------------------------------------------------------------
@@ -891,11 +948,19 @@ class Match:
     every evaluation of a game in a round is done by the net of its root player.  Mirrors
     Selfplay's stepping and inspection interface; there are no training rows.
     search: a SearchParams to start from instead of default_match_params(); keyword
-    overrides apply on top of either."""
+    overrides apply on top of either.
+    sides (coffee_match_create2): a pair, side 0 (the baseline's side) then side 1 (the
+    candidate's), each a dict of SearchParams / UncertaintyParams field overrides on top of
+    the engine's search (uncertainty off), or a (SearchParams, UncertaintyParams) pair.  Every
+    search then runs with the parameters of the side that searches; set_uncertainty is
+    refused.  The game-level settings (init_games_with_policy and its two area settings) stay
+    the engine's.
+    share_net: both sides on one network instance (equal paths required): one launch a round
+    and one evaluation cache."""
 
     def __init__(self, X=5, Y=5, W=4, num_games=128, baseline_path=None, candidate_path=None, seed=1, slot_base=0,
                  node_cap=0, commit_interval=0, nn_cache_log2=0, nn_batch_cap=0, nn_precision="default",
-                 start_stagger=0, engines_per_device=0, search=None, **search_over):
+                 start_stagger=0, engines_per_device=0, search=None, sides=None, share_net=False, **search_over):
         self.X, self.Y, self.W = X, Y, W
         self.A, self.P = X * Y, 4 * X * Y
         self.num_games = num_games
@@ -920,7 +985,19 @@ class Match:
         cfg.engines_per_device = engines_per_device
         self.cfg = cfg
         self.h = ctypes.c_void_p()
-        check(lib().coffee_match_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+        if sides is None and not share_net:
+            check(lib().coffee_match_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+            return
+        opts = MatchOptions()
+        opts.share_net = 1 if share_net else 0
+        if sides is not None:
+            if not isinstance(sides, (tuple, list)) or len(sides) != 2:
+                raise CoffeeError("Match sides: a pair (side 0, side 1)")
+            opts.per_side = 1
+            for i in range(2):
+                opts.side[i] = _match_side(search, sides[i], i)
+        self.opts = opts
+        check(lib().coffee_match_create2(ctypes.byref(cfg), ctypes.byref(opts), ctypes.byref(self.h)))
 
     def step(self, rounds, stream=None):
         check(lib().coffee_match_step(self.h, rounds, stream))

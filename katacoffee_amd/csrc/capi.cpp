@@ -1,6 +1,7 @@
 // C ABI (include/katacoffee.h): argument checking, error capture, dispatch.
 // No C++ exception crosses this boundary; failures return COFFEE_E* with the
 // message in coffee_last_error().
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -462,17 +463,50 @@ struct coffee_match {
   SelfplayEngine* eng;
 };
 
-int coffee_match_create(const coffee_match_config* cfg, coffee_match** out) {
+int coffee_match_create2(const coffee_match_config* cfg, const coffee_match_options* opts, coffee_match** out) {
   return guarded([&] {
     need(cfg && out, "NULL argument");
     coffee_match* h = new coffee_match{nullptr};
     try {
-      h->eng = new SelfplayEngine(*cfg);  // validates the config before its first HIP call
+      h->eng = new SelfplayEngine(*cfg, opts);  // validates config and options before its first HIP call
     } catch(...) {
       delete h;
       throw;
     }
     *out = h;
+  });
+}
+
+int coffee_match_create(const coffee_match_config* cfg, coffee_match** out) {
+  return coffee_match_create2(cfg, nullptr, out);
+}
+
+int coffee_match_elo(int64_t wins, int64_t draws, int64_t losses, double* score, double* elo, double* elo_lo,
+                     double* elo_hi, double* los) {
+  return guarded([&] {
+    need(wins >= 0 && draws >= 0 && losses >= 0, "wins, draws and losses must be >= 0");
+    need(wins + draws + losses > 0, "no games: wins + draws + losses must be > 0");
+    const double W = (double)wins, D = (double)draws, L = (double)losses, N = W + D + L;
+    const double p = (W + D / 2.0) / N;
+    const double var = (W * (1.0 - p) * (1.0 - p) + D * (0.5 - p) * (0.5 - p) + L * p * p) / N;
+    const double se = std::sqrt(var / N);
+    auto eloOf = [](double x) {
+      if(x <= 0.0)
+        return -HUGE_VAL;
+      if(x >= 1.0)
+        return HUGE_VAL;
+      return -400.0 * std::log10(1.0 / x - 1.0);
+    };
+    if(score)
+      *score = p;
+    if(elo)
+      *elo = eloOf(p);
+    if(elo_lo)
+      *elo_lo = eloOf(p - 1.96 * se);
+    if(elo_hi)
+      *elo_hi = eloOf(p + 1.96 * se);
+    if(los)
+      *los = W + L > 0.0 ? 0.5 * std::erfc(-(W - L) / std::sqrt(2.0 * (W + L))) : 0.5;
   });
 }
 

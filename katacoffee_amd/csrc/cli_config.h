@@ -64,13 +64,34 @@ struct Settings {
   StartPosSettings startPos;  // off unless startPosesProb > 0 and a source is named
 };
 
-inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& s) {
+// The typed lookups of a config map.  suffix (the `katago match` bot index, "0" / "1"; empty:
+// none): a key is read as key<suffix> where the file has that, else as the plain key -- the
+// reference's precedence for per-bot search keys (Setup::loadParams, setup.cpp).
+struct ConfigReader {
+  const std::map<std::string, std::string>& kv;
+  std::string suffix;
+  // the entry a key resolves to (kv.end(): absent); name: the key as the file spells it
+  std::map<std::string, std::string>::const_iterator find(const char* k, std::string& name) const {
+    if(!suffix.empty()) {
+      auto it = kv.find(k + suffix);
+      if(it != kv.end()) {
+        name = k + suffix;
+        return it;
+      }
+    }
+    name = k;
+    return kv.find(k);
+  }
+  bool has(const char* k) const {
+    std::string n;
+    return find(k, n) != kv.end();
+  }
   // a value that is not a whole number of the key's type is an error naming the key
   // (the reference's ConfigParser::getInt / getFloat throw IOError the same way)
-  auto bad = [](const char* k, const std::string& v) {
-    return std::invalid_argument(std::string("config key ") + k + ": bad value '" + v + "'");
-  };
-  auto parseInt = [&](const char* k, const std::string& v) {
+  static std::invalid_argument bad(const std::string& k, const std::string& v) {
+    return std::invalid_argument("config key " + k + ": bad value '" + v + "'");
+  }
+  static int parseInt(const std::string& k, const std::string& v) {
     size_t used = 0;
     int r = 0;
     try {
@@ -81,43 +102,132 @@ inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& 
     if(used != v.size())
       throw bad(k, v);
     return r;
-  };
-  auto geti = [&](const char* k, int& v) {
-    auto it = kv.find(k);
+  }
+  void geti(const char* k, int& v) const {
+    std::string n;
+    auto it = find(k, n);
     if(it != kv.end())
-      v = parseInt(k, it->second);
-  };
-  auto getf = [&](const char* k, float& v) {
-    auto it = kv.find(k);
+      v = parseInt(n, it->second);
+  }
+  void getf(const char* k, float& v) const {
+    std::string n;
+    auto it = find(k, n);
     if(it == kv.end())
       return;
     size_t used = 0;
     try {
       v = std::stof(it->second, &used);
     } catch(const std::exception&) {
-      throw bad(k, it->second);
+      throw bad(n, it->second);
     }
     if(used != it->second.size())
-      throw bad(k, it->second);
-  };
-  auto getb = [&](const char* k, int32_t& v) {
-    auto it = kv.find(k);
+      throw bad(n, it->second);
+  }
+  void getb(const char* k, int32_t& v) const {
+    std::string n;
+    auto it = find(k, n);
     if(it != kv.end())
       v = (it->second == "true" || it->second == "True" || it->second == "1") ? 1 : 0;
-  };
+  }
+  // a value outside [lo, hi] (NaN included) is an error naming the key, like
+  // ConfigParser::getDouble(key, min, max)
+  void getfIn(const char* k, float& v, float lo, float hi) const {
+    std::string n;
+    if(find(k, n) == kv.end())
+      return;
+    getf(k, v);
+    if(!(v >= lo && v <= hi))
+      throw std::invalid_argument("config key " + n + ": value " + std::to_string(v) + " outside [" +
+                                  std::to_string(lo) + ", " + std::to_string(hi) + "]");
+  }
+  void gets(const char* k, std::string& v) const {
+    std::string n;
+    auto it = find(k, n);
+    if(it != kv.end())
+      v = it->second;
+  }
+};
+
+// The search keys and the four uncertainty keys onto p / unc (r.suffix: the bot of `katago match`).
+inline void applySearchConfig(const ConfigReader& r, coffee_search_params& p, coffee_uncertainty_params& unc) {
+  r.geti("maxVisits", p.max_visits);
+  r.getf("cpuctExploration", p.cpuct_exploration);
+  r.getf("cpuctExplorationLog", p.cpuct_exploration_log);
+  r.getf("cpuctExplorationBase", p.cpuct_exploration_base);
+  r.getf("fpuReductionMax", p.fpu_reduction_max);
+  r.getf("rootFpuReductionMax", p.root_fpu_reduction_max);
+  r.getf("fpuLossProp", p.fpu_loss_prop);
+  r.getf("rootFpuLossProp", p.root_fpu_loss_prop);
+  r.getb("fpuParentWeightByVisitedPolicy", p.fpu_parent_weight_by_visited_policy);
+  r.getf("fpuParentWeightByVisitedPolicyPow", p.fpu_parent_weight_by_visited_policy_pow);
+  r.getf("valueWeightExponent", p.value_weight_exponent);
+  r.getb("rootNoiseEnabled", p.root_noise_enabled);
+  r.getf("rootDirichletNoiseTotalConcentration", p.root_dirichlet_noise_total_concentration);
+  r.getf("rootDirichletNoiseWeight", p.root_dirichlet_noise_weight);
+  r.getf("rootPolicyTemperature", p.root_policy_temperature);
+  r.getf("rootPolicyTemperatureEarly", p.root_policy_temperature_early);
+  r.getf("rootDesiredPerChildVisitsCoeff", p.root_desired_per_child_visits_coeff);
+  r.geti("rootNumSymmetriesToSample", p.root_num_symmetries_to_sample);
+  r.getf("chosenMoveTemperature", p.chosen_move_temperature);
+  r.getf("chosenMoveTemperatureEarly", p.chosen_move_temperature_early);
+  r.getf("chosenMoveTemperatureHalflife", p.chosen_move_temperature_halflife);
+  r.getf("chosenMoveSubtract", p.chosen_move_subtract);
+  r.getf("chosenMovePrune", p.chosen_move_prune);
+  r.getb("useLcbForSelection", p.use_lcb_for_selection);
+  r.getf("lcbStdevs", p.lcb_stdevs);
+  r.getf("minVisitPropForLCB", p.min_visit_prop_for_lcb);
+  r.getf("subtreeValueBiasFactor", p.subtree_value_bias_factor);
+  r.getf("subtreeValueBiasWeightExponent", p.subtree_value_bias_weight_exponent);
+  r.getf("subtreeValueBiasFreeProp", p.subtree_value_bias_free_prop);
+  r.getb("useGraphSearch", p.use_graph_search);
+  // PlaySettings (playsettings.cpp:80-99)
+  r.getf("cheapSearchProb", p.cheap_search_prob);
+  r.geti("cheapSearchVisits", p.cheap_search_visits);
+  r.getf("cheapSearchTargetWeight", p.cheap_search_target_weight);
+  r.getb("reduceVisits", p.reduce_visits);
+  r.getf("reduceVisitsThreshold", p.reduce_visits_threshold);
+  r.geti("reduceVisitsThresholdLookback", p.reduce_visits_threshold_lookback);
+  r.geti("reducedVisitsMin", p.reduced_visits_min);
+  r.getf("reducedVisitsWeight", p.reduced_visits_weight);
+  r.getf("policySurpriseDataWeight", p.policy_surprise_data_weight);
+  r.getf("valueSurpriseDataWeight", p.value_surprise_data_weight);
+  r.getb("initGamesWithPolicy", p.init_games_with_policy);
+  r.getf("policyInitAreaProp", p.policy_init_area_prop);
+  r.getf("policyInitAreaTemperature", p.policy_init_area_temperature);
+  r.getf("earlyForkGameProb", p.early_fork_game_prob);
+  r.getf("earlyForkGameExpectedMoveProp", p.early_fork_game_expected_move_prop);
+  r.getf("forkGameProb", p.fork_game_prob);
+  r.geti("forkGameMinChoices", p.fork_game_min_choices);
+  r.geti("earlyForkGameMaxChoices", p.early_fork_game_max_choices);
+  r.geti("forkGameMaxChoices", p.fork_game_max_choices);
+  r.getf("sidePositionProb", p.side_position_prob);
+  // PlaySettings fields the reference's loader never reads (playsettings.cpp:14): accepted
+  // here so the recording can be switched on from a config
+  r.getb("recordTreePositions", p.record_tree_positions);
+  r.geti("recordTreeThreshold", p.record_tree_threshold);
+  r.getf("recordTreeTargetWeight", p.record_tree_target_weight);
+  // uncertainty weighting, with the reference's ranges (setup.cpp:539-562)
+  r.getb("useUncertainty", unc.use_uncertainty);
+  r.getfIn("uncertaintyCoeff", unc.uncertainty_coeff, 0.0001f, 1.0f);
+  r.getfIn("uncertaintyExponent", unc.uncertainty_exponent, 0.0f, 2.0f);
+  r.getfIn("uncertaintyMaxWeight", unc.uncertainty_max_weight, 1.0f, 100.0f);
+}
+
+inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& s) {
+  const ConfigReader r{kv, ""};
   auto it = kv.find("bSizes");
   if(it != kv.end())
-    s.x = s.y = parseInt("bSizes", trim(it->second.substr(0, it->second.find(','))));
-  geti("boardXLen", s.x);
-  geti("boardYLen", s.y);
-  geti("winLen", s.winLen);
-  geti("numGameThreads", s.games);
-  geti("numGamesPerGpu", s.games);
-  geti("numGpus", s.gpus);
-  geti("numNNServerThreadsPerModel", s.servers);
-  geti("maxRowsPerTrainFile", s.maxRowsPerFile);
-  getf("modelPollSeconds", s.modelPollSeconds);
-  geti("nnCacheSizePowerOfTwo", s.nnCacheLog2);  // setup.cpp:268; <= 0 disables the cache
+    s.x = s.y = ConfigReader::parseInt("bSizes", trim(it->second.substr(0, it->second.find(','))));
+  r.geti("boardXLen", s.x);
+  r.geti("boardYLen", s.y);
+  r.geti("winLen", s.winLen);
+  r.geti("numGameThreads", s.games);
+  r.geti("numGamesPerGpu", s.games);
+  r.geti("numGpus", s.gpus);
+  r.geti("numNNServerThreadsPerModel", s.servers);
+  r.geti("maxRowsPerTrainFile", s.maxRowsPerFile);
+  r.getf("modelPollSeconds", s.modelPollSeconds);
+  r.geti("nnCacheSizePowerOfTwo", s.nnCacheLog2);  // setup.cpp:268; <= 0 disables the cache
   s.nnCacheLog2 = std::max(0, s.nnCacheLog2);
   it = kv.find("nnPrecision");
   if(it != kv.end()) {
@@ -134,89 +244,44 @@ inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& 
     else
       throw std::invalid_argument("nnPrecision must be auto, corrected, accurate, fast or fastLayered");
   }
-  coffee_search_params& p = s.sp;
-  geti("maxVisits", p.max_visits);
-  getf("cpuctExploration", p.cpuct_exploration);
-  getf("cpuctExplorationLog", p.cpuct_exploration_log);
-  getf("cpuctExplorationBase", p.cpuct_exploration_base);
-  getf("fpuReductionMax", p.fpu_reduction_max);
-  getf("rootFpuReductionMax", p.root_fpu_reduction_max);
-  getf("fpuLossProp", p.fpu_loss_prop);
-  getf("rootFpuLossProp", p.root_fpu_loss_prop);
-  getb("fpuParentWeightByVisitedPolicy", p.fpu_parent_weight_by_visited_policy);
-  getf("fpuParentWeightByVisitedPolicyPow", p.fpu_parent_weight_by_visited_policy_pow);
-  getf("valueWeightExponent", p.value_weight_exponent);
-  getb("rootNoiseEnabled", p.root_noise_enabled);
-  getf("rootDirichletNoiseTotalConcentration", p.root_dirichlet_noise_total_concentration);
-  getf("rootDirichletNoiseWeight", p.root_dirichlet_noise_weight);
-  getf("rootPolicyTemperature", p.root_policy_temperature);
-  getf("rootPolicyTemperatureEarly", p.root_policy_temperature_early);
-  getf("rootDesiredPerChildVisitsCoeff", p.root_desired_per_child_visits_coeff);
-  geti("rootNumSymmetriesToSample", p.root_num_symmetries_to_sample);
-  getf("chosenMoveTemperature", p.chosen_move_temperature);
-  getf("chosenMoveTemperatureEarly", p.chosen_move_temperature_early);
-  getf("chosenMoveTemperatureHalflife", p.chosen_move_temperature_halflife);
-  getf("chosenMoveSubtract", p.chosen_move_subtract);
-  getf("chosenMovePrune", p.chosen_move_prune);
-  getb("useLcbForSelection", p.use_lcb_for_selection);
-  getf("lcbStdevs", p.lcb_stdevs);
-  getf("minVisitPropForLCB", p.min_visit_prop_for_lcb);
-  getf("subtreeValueBiasFactor", p.subtree_value_bias_factor);
-  getf("subtreeValueBiasWeightExponent", p.subtree_value_bias_weight_exponent);
-  getf("subtreeValueBiasFreeProp", p.subtree_value_bias_free_prop);
-  getb("useGraphSearch", p.use_graph_search);
-  // PlaySettings (playsettings.cpp:80-99)
-  getf("cheapSearchProb", p.cheap_search_prob);
-  geti("cheapSearchVisits", p.cheap_search_visits);
-  getf("cheapSearchTargetWeight", p.cheap_search_target_weight);
-  getb("reduceVisits", p.reduce_visits);
-  getf("reduceVisitsThreshold", p.reduce_visits_threshold);
-  geti("reduceVisitsThresholdLookback", p.reduce_visits_threshold_lookback);
-  geti("reducedVisitsMin", p.reduced_visits_min);
-  getf("reducedVisitsWeight", p.reduced_visits_weight);
-  getf("policySurpriseDataWeight", p.policy_surprise_data_weight);
-  getf("valueSurpriseDataWeight", p.value_surprise_data_weight);
-  getb("initGamesWithPolicy", p.init_games_with_policy);
-  getf("policyInitAreaProp", p.policy_init_area_prop);
-  getf("policyInitAreaTemperature", p.policy_init_area_temperature);
-  getf("earlyForkGameProb", p.early_fork_game_prob);
-  getf("earlyForkGameExpectedMoveProp", p.early_fork_game_expected_move_prop);
-  getf("forkGameProb", p.fork_game_prob);
-  geti("forkGameMinChoices", p.fork_game_min_choices);
-  geti("earlyForkGameMaxChoices", p.early_fork_game_max_choices);
-  geti("forkGameMaxChoices", p.fork_game_max_choices);
-  getf("sidePositionProb", p.side_position_prob);
-  // PlaySettings fields the reference's loader never reads (playsettings.cpp:14): accepted
-  // here so the recording can be switched on from a config
-  getb("recordTreePositions", p.record_tree_positions);
-  geti("recordTreeThreshold", p.record_tree_threshold);
-  getf("recordTreeTargetWeight", p.record_tree_target_weight);
-  // uncertainty weighting, with the reference's ranges (setup.cpp:539-562); a value outside
-  // them (NaN included) is an error naming the key, like ConfigParser::getDouble(key, min, max)
-  auto getfIn = [&](const char* k, float& v, float lo, float hi) {
-    if(kv.find(k) == kv.end())
-      return;
-    getf(k, v);
-    if(!(v >= lo && v <= hi))
-      throw std::invalid_argument(std::string("config key ") + k + ": value " + std::to_string(v) +
-                                  " outside [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
-  };
-  getb("useUncertainty", s.unc.use_uncertainty);
-  getfIn("uncertaintyCoeff", s.unc.uncertainty_coeff, 0.0001f, 1.0f);
-  getfIn("uncertaintyExponent", s.unc.uncertainty_exponent, 0.0f, 2.0f);
-  getfIn("uncertaintyMaxWeight", s.unc.uncertainty_max_weight, 1.0f, 100.0f);
+  applySearchConfig(r, s.sp, s.unc);
   // start positions (play.cpp:186-196 getters: the same ranges)
-  auto gets = [&](const char* k, std::string& v) {
-    auto f = kv.find(k);
-    if(f != kv.end())
-      v = f->second;
-  };
-  gets("startPosesFromSgfDir", s.startPos.sgfDirs);
-  gets("startPosesFile", s.startPos.file);
-  getfIn("startPosesProb", s.startPos.params.prob, 0.0f, 1.0f);
-  getfIn("startPosesLoadProb", s.startPos.loadProb, 0.0f, 1.0f);
-  getfIn("startPosesTurnWeightLambda", s.startPos.params.turn_weight_lambda, -10.0f, 10.0f);
-  getfIn("startPosesPolicyInitAreaProp", s.startPos.params.start_policy_init_area_prop, 0.0f, 1.0f);
+  r.gets("startPosesFromSgfDir", s.startPos.sgfDirs);
+  r.gets("startPosesFile", s.startPos.file);
+  r.getfIn("startPosesProb", s.startPos.params.prob, 0.0f, 1.0f);
+  r.getfIn("startPosesLoadProb", s.startPos.loadProb, 0.0f, 1.0f);
+  r.getfIn("startPosesTurnWeightLambda", s.startPos.params.turn_weight_lambda, -10.0f, 10.0f);
+  r.getfIn("startPosesPolicyInitAreaProp", s.startPos.params.start_policy_init_area_prop, 0.0f, 1.0f);
+}
+
+
+// `katago match` (cli_match.cpp): the two bots of a match config, as the reference's
+// match_example.cfg names them.  Every search key and the four uncertainty keys resolve as
+// key<i> over key over the default the caller put into `def`; nnModelFile<i> over nnModelFile.
+struct MatchBot {
+  std::string name, model;
+  coffee_search_params sp;
+  coffee_uncertainty_params unc;
+};
+
+inline void applyMatchBots(const std::map<std::string, std::string>& kv, const coffee_search_params& defSp,
+                           const coffee_uncertainty_params& defUnc, MatchBot bots[2]) {
+  {
+    auto it = kv.find("numBots");
+    if(it != kv.end() && ConfigReader::parseInt("numBots", it->second) != 2)
+      throw std::invalid_argument("config key numBots: this command plays exactly 2 bots, numBots must be 2 (got " +
+                                  it->second + ")");
+  }
+  for(int i = 0; i < 2; i++) {
+    const ConfigReader r{kv, std::to_string(i)};
+    bots[i].sp = defSp;
+    bots[i].unc = defUnc;
+    applySearchConfig(r, bots[i].sp, bots[i].unc);
+    bots[i].name = "bot" + std::to_string(i);
+    r.gets("botName", bots[i].name);
+    bots[i].model.clear();
+    r.gets("nnModelFile", bots[i].model);
+  }
 }
 
 }  // namespace kccli

@@ -310,6 +310,9 @@ int gatekeeperMain(int argc, char** argv);  // cli_gatekeeper.cpp
 #ifdef KATAGO_ANALYSIS
 int analysisMain(int argc, char** argv);  // cli_analysis.cpp
 #endif
+#ifdef KATAGO_MATCH
+int matchMain(int argc, char** argv);  // cli_match.cpp
+#endif
 
 int main(int argc, char** argv) {
 #ifdef KATAGO_GATEKEEPER
@@ -320,6 +323,10 @@ int main(int argc, char** argv) {
 #ifdef KATAGO_ANALYSIS
   if(argc >= 2 && std::string(argv[1]) == "analysis")
     return analysisMain(argc, argv);
+#endif
+#ifdef KATAGO_MATCH
+  if(argc >= 2 && std::string(argv[1]) == "match")
+    return matchMain(argc, argv);
 #endif
   if(argc < 2 || std::string(argv[1]) != "selfplay")
     die("usage: katago selfplay -config <cfg> -models-dir <dir> -output-dir <dir> [-max-games-total N] "

@@ -390,6 +390,13 @@ struct SearchDev {
   float spInitAreaProp;                       // startPosesPolicyInitAreaProp
   int32_t spPad;
   DPtr<unsigned long long> spGames;           // games started from the table so far
+  // per-side match settings (coffee_match_create2), read by the MATCH kernel
+  // instantiations only (new members stay last: the offsets above are the other kernels').
+  // matchPerSide: the searches of side 1 (matchNet) run with sp1 / unc1, side 0's with sp / unc.
+  // matchSharedNet: both sides are evaluated by net 0 (one list, one cache, one launch a round).
+  int32_t matchPerSide, matchSharedNet;
+  SP sp1;
+  Unc unc1;
 };
 
 // Match play: the candidate (net 1) plays black (player 1) in game number n of global

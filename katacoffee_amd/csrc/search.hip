@@ -144,10 +144,11 @@ struct GV {
   const DTables& T;
   int g, lane;
   const SP* sp;  // this move's search parameters (moveParams after loadGame)
+  const Unc* unc;  // and its uncertainty weighting (match play: the searching side's, bindGame)
   mutable int esel = 0;  // the game's current edge-pool buffer (GameDev::edgeSel; setEdgeSel)
-  KC_D GV(const SearchDev& d_, int g_) : d(d_), T(*d_.T), g(g_), lane(laneId()), sp(&d_.sp) {}
+  KC_D GV(const SearchDev& d_, int g_) : d(d_), T(*d_.T), g(g_), lane(laneId()), sp(&d_.sp), unc(&d_.unc) {}
   // tables through a readonly noalias kernel argument: uniform reads become scalar loads
-  KC_D GV(const SearchDev& d_, const DTables& t_, int g_) : d(d_), T(t_), g(g_), lane(laneId()), sp(&d_.sp) {}
+  KC_D GV(const SearchDev& d_, const DTables& t_, int g_) : d(d_), T(t_), g(g_), lane(laneId()), sp(&d_.sp), unc(&d_.unc) {}
   KC_D Node* nodes() const { return d.nodes + (size_t)g * d.cap; }
   KC_D Edge* inlineEdges(int n) const { return d.edges + ((size_t)g * d.cap + n) * INLINE_EDGES; }
   KC_D Edge* edgePool() const { return d.edgePool + ((size_t)g * 2 + esel) * d.edgePoolCap; }
@@ -184,21 +185,47 @@ KC_D void storeGame(const GV& v, const GameDev& s) {
     dst[i] = src[i];
 }
 
+// Match play: the side (0 / 1) that searches a game's current root, or has just searched it
+// (the root and the game number change only in kCommit and in a policy-initialisation backup).
+KC_D int sideOf(const SearchDev& d, int g, const GameDev& s) {
+  return matchNet(d.slotBase + g, s.gameNum, s.root.pla);
+}
+
 // The view's per-game settings from the loaded state.
+// MATCH with per-side settings: side 1's searches read sp1 / unc1 (match play
+// admits no cheap searches, so a side has one parameter set).
+template <bool MATCH = false>
 KC_D void bindGame(GV& v, const GameDev& s) {
   // a cheap search without recorded rows runs without root noise and root-specific
   // settings (runBotWithLimits play.cpp:1024-1037); the flag is uniform
   v.sp = __builtin_amdgcn_readfirstlane(s.noNoise) ? &v.d.spCheap : &v.d.sp;
+  if constexpr(MATCH) {
+    if(v.d.matchPerSide && __builtin_amdgcn_readfirstlane(sideOf(v.d, v.g, s))) {
+      v.sp = &v.d.sp1;
+      v.unc = &v.d.unc1;
+    }
+  }
   v.setEdgeSel(s.edgeSel);
 }
 
+// MATCH with per-side settings: the visit limit of the search about to start is the next
+// mover's (setMoveLimits gave side 0's; match play has no cheap or reduced searches).
+template <bool MATCH>
+KC_D void matchMoveLimits(const GV& v, GameDev& s) {
+  if constexpr(MATCH) {
+    if(v.d.matchPerSide && __builtin_amdgcn_readfirstlane(sideOf(v.d, v.g, s)))
+      s.visitLimit = v.d.sp1.maxVisits;
+  }
+}
+
+template <bool MATCH = false>
 KC_D void loadGame(GV& v, GameDev& s) {
   const uint32_t* src = reinterpret_cast<const uint32_t*>(&v.d.games[v.g]);
   uint32_t* dst = reinterpret_cast<uint32_t*>(&s);
   for(int i = v.lane; i < (int)(sizeof(GameDev) / 4); i += 64)
     dst[i] = src[i];
   waveSync();
-  bindGame(v, s);
+  bindGame<MATCH>(v, s);
 }
 
 template <int NI>
@@ -1177,8 +1204,9 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
 // lookup and the cache write all go through it.  The root and the game number it reads
 // change only in kCommit (and in a policy-initialisation backup, after its evaluation is
 // consumed), so a round's select, compaction and backup agree, also for a deferred row.
+// With a shared net (matchSharedNet) both sides are net 0: one list, one cache, one launch.
 KC_D int netOf(const SearchDev& d, int g, const GameDev& s) {
-  return matchNet(d.slotBase + g, s.gameNum, s.root.pla);
+  return d.matchSharedNet ? 0 : sideOf(d, g, s);
 }
 struct NNCache {
   uint64_t* key;
@@ -1280,9 +1308,9 @@ KC_D void selectBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
     return;
   }
   if(loaded)
-    bindGame(v, s);
+    bindGame<MATCH>(v, s);
   else
-    loadGame(v, s);
+    loadGame<MATCH>(v, s);
   if(s.phase == PH_COMMIT || s.startDelay > 0) {
     s.leafKind = LEAF_NONE;
     if(loaded) {
@@ -1712,7 +1740,7 @@ KC_D const T* uniformConst(const T* p) {
   asm volatile("" : "+s"(q));
   return (const T*)q;
 }
-template <int NI>
+template <int NI, bool MATCH = false>
 __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, int g, GameDev* gs, float* scratch) {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   const SearchDev& d = *uniformConst(dp);
@@ -1720,13 +1748,14 @@ __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, in
   scratch = uniformPtr(scratch);
   g = __builtin_amdgcn_readfirstlane(g);
   GV v(d, *uniformConst(Tp), g);
-  bindGame(v, s);
+  bindGame<MATCH>(v, s);
   const SP& sp = *v.sp;
   const int P = d.P;
   const float* o = d.nnOut + (size_t)s.nnSlot * (P + 4);
   bool needCommit = false;
   if(s.leafKind == LEAF_INIT) {
     needCommit = initMove<NI>(v, s, o, scratch);
+    matchMoveLimits<MATCH>(v, s);  // the first searched move's limit, by its mover
   } else if(s.leafKind == LEAF_FORK) {
     forkEval<NI>(v, s, o, scratch);
   } else if(s.leafKind == LEAF_SIDE) {
@@ -1739,7 +1768,7 @@ __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, in
     waveSync();
     // the short-term error is averaged over the sampled symmetries like win / loss
     // (nninputs.cpp:108-119); the root's weight comes from the average
-    const float err = d.unc.on ? stErrorOf(st) : 0.0f;
+    const float err = v.unc->on ? stErrorOf(st) : 0.0f;
     float* acc = v.accPolicy();
     if(s.rootK == 0) {
       for(int p = v.lane; p < P; p += 64) {
@@ -1775,7 +1804,7 @@ __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, in
         Node* r = &v.nodes()[s.rootIdx];
         r->nnWin = s.accWin / fl;
         r->nnLoss = s.accLoss / fl;
-        r->nnWeight = uncWeightOf(d.unc, s.accErr / fl);
+        r->nnWeight = uncWeightOf(*v.unc, s.accErr / fl);
         r->flags |= 1;
       }
       waveSync();
@@ -1807,7 +1836,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   SPROF_INIT();
   const unsigned long long t0 = SPROF_NOW();
   (void)t0;
-  loadGame(v, s);
+  loadGame<MATCH>(v, s);
   if(s.leafKind == LEAF_NONE)
     return true;
   unsigned long long tPost = 0, tLeaf = 0, tPath = 0;
@@ -1818,7 +1847,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   const float* o = d.nnOut + (size_t)s.nnSlot * (P + 4);
   bool needCommit = false;
   if(s.leafKind == LEAF_INIT || s.leafKind == LEAF_FORK || s.leafKind == LEAF_SIDE || s.leafKind == LEAF_ROOTEVAL) {
-    needCommit = rareLeaf<NI>(&d, &T, g, &s, scratch);
+    needCommit = rareLeaf<NI, MATCH>(&d, &T, g, &s, scratch);
   } else {
     NStats leafSt{0u, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     bool haveLeaf = false;
@@ -1845,7 +1874,13 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
       } else {
         float st;
         postprocess<NI>(v, s.leaf, s.leafSym, o, pol, w, l, st, scratch, pv);
-        if(d.unc.on)
+        // MATCH with a shared net: the cache entry written below serves both sides, so it carries the
+        // error whenever either side weights by it (the side with the setting off ignores it:
+        // uncWeightOf gives 1)
+        bool wantErr = v.unc->on != 0;
+        if constexpr(MATCH)
+          wantErr = wantErr || (d.matchSharedNet && (d.unc.on | d.unc1.on) != 0);
+        if(wantErr)
           err = stErrorOf(st);
         if(d.cacheOn) {
           // kCompact bid this evaluation for the state's cache slot (atomicMax of
@@ -1875,7 +1910,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
         }
       }
       firstExpansion<NI>(v, s.leafNode, pv);
-      const float weight = uncWeightOf(d.unc, err);
+      const float weight = uncWeightOf(*v.unc, err);
       if(v.lane == 0) {
         Node* n = &v.nodes()[s.leafNode];
         n->nnWin = w;
@@ -1892,7 +1927,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
       tLeaf = SPROF_NOW() - tb;
     } else if(s.leafKind == LEAF_TERMINAL) {
       float val = s.leaf.winner == 2 ? 1.0f : (s.leaf.winner == 1 ? -1.0f : 0.0f);
-      leafSt = addLeafValue(v, s, s.leafNode, val, uncTerminalWeight(d.unc), true, false);
+      leafSt = addLeafValue(v, s, s.leafNode, val, uncTerminalWeight(*v.unc), true, false);
       haveLeaf = true;
     } else if(s.leafKind == LEAF_NOCHILD) {
       const Node& n = v.nodes()[s.leafNode];
@@ -3624,8 +3659,9 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
   GV v(d, *Tp, g);
   SPROF_INIT();
   [[maybe_unused]] const unsigned long long t0 = SPROF_NOW();
-  loadGame(v, s);
-  const SP& sp = d.sp;
+  loadGame<MATCH>(v, s);
+  // MATCH: the mover's own parameters (per-side settings; equal to d.sp without them)
+  const SP& sp = MATCH ? *v.sp : d.sp;
   const int P = d.P, A = d.A;
   DRng rng{s.rngSeed, s.rngCtr};
   if(s.root.finished) {
@@ -3636,6 +3672,7 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
     s.gameNum++;
     s.sideNext = 0;
     afterGame(v, s, rng, reinterpret_cast<uint16_t*>(lds), true);
+    matchMoveLimits<MATCH>(v, s);
     waveSync();
     storeGame(v, s);
     return;
@@ -3751,6 +3788,9 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
     s.phase = PH_ROOTEVAL;
     s.rootK = 0;
   }
+  // the next search's limit by its mover: the other side, or after a game's end the next
+  // game's first mover (the colours, and with them the sides, have swapped)
+  matchMoveLimits<MATCH>(v, s);
   waveSync();
   storeGame(v, s);
   SPROF_ADD(16, 1);
@@ -4063,11 +4103,24 @@ __global__ void __launch_bounds__(64) kInit(const SearchDev* __restrict__ dp, co
   storeGame(v, s);
 }
 
+// Per-side match settings, after kInit: a first game whose first mover is side 1 searches
+// to side 1's limit (kInit's startGame gave side 0's).  One thread per game.
+__global__ void __launch_bounds__(256) kMatchSideLimits(const SearchDev* __restrict__ dp) {
+  const SearchDev& d = *dp;
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if(g >= d.G)
+    return;
+  GameDev* s = d.games + g;
+  if(matchNet(d.slotBase + g, s->gameNum, s->root.pla))
+    s->visitLimit = d.sp1.maxVisits;
+}
+
 // Canonical breadth-first export of one game's tree (tests / tools).
 // nodesOut [maxNodes][24] u32, edgesOut [maxNodes][P][3] u32 (child bfs index, edge visits, move).
-__global__ void kGameTree(const SearchDev* __restrict__ dp, int g, int maxNodes, uint32_t* nodesOut,
-                          uint32_t* edgesOut, int32_t* count) {
-  const SearchDev& d = *dp;
+// SIDES (per-side match settings): word 21 follows the setting of the side whose search built the tree.
+template <bool SIDES>
+KC_D void gameTreeBody(const SearchDev& d, int g, int maxNodes, uint32_t* nodesOut, uint32_t* edgesOut,
+                       int32_t* count) {
   if(threadIdx.x != 0)
     return;
   const GameDev& s = d.games[g];
@@ -4076,6 +4129,9 @@ __global__ void kGameTree(const SearchDev* __restrict__ dp, int g, int maxNodes,
     *count = 0;
     return;
   }
+  [[maybe_unused]] int32_t sideOn = 0;
+  if constexpr(SIDES)
+    sideOn = sideOf(d, g, s) ? d.unc1.on : d.unc.on;
   // canonical index map kept in nodesOut word 23 of each discovered node: store original idx
   int n = 0;
   int head = 0;
@@ -4116,7 +4172,7 @@ __global__ void kGameTree(const SearchDev* __restrict__ dp, int g, int maxNodes,
     o[19] = (uint32_t)(uint64_t)sw;
     o[20] = (uint32_t)((uint64_t)sw >> 32);
     // the node's own evaluation weight with uncertainty weighting on (off: 0, as before)
-    o[21] = d.unc.on ? f2u(x.nnWeight) : 0u;
+    o[21] = (SIDES ? sideOn : d.unc.on) ? f2u(x.nnWeight) : 0u;
     o[22] = 0;
     const NodeEdges E{d.edges + ((size_t)g * d.cap + idx) * INLINE_EDGES,
                       d.edgePool + ((size_t)g * 2 + d.games[g].edgeSel) * d.edgePoolCap + x.edgeBase};
@@ -4143,6 +4199,19 @@ __global__ void kGameTree(const SearchDev* __restrict__ dp, int g, int maxNodes,
   for(int q = 0; q < n; q++)
     nodesOut[(size_t)q * 24 + 23] = 0;
   *count = n;
+}
+
+__global__ void kGameTree(const SearchDev* __restrict__ dp, int g, int maxNodes, uint32_t* nodesOut,
+                          uint32_t* edgesOut, int32_t* count) {
+  gameTreeBody<false>(*dp, g, maxNodes, nodesOut, edgesOut, count);
+}
+// The same export once more for an engine with per-side match settings (any other returns at
+// once): launchGameTree has the device copy of SearchDev only, and kGameTree stays as it is.
+__global__ void kGameTreeSides(const SearchDev* __restrict__ dp, int g, int maxNodes, uint32_t* nodesOut,
+                               uint32_t* edgesOut, int32_t* count) {
+  if(!dp->matchPerSide)
+    return;
+  gameTreeBody<true>(*dp, g, maxNodes, nodesOut, edgesOut, count);
 }
 
 // ---------------------------------------------------------------------------
@@ -4508,6 +4577,10 @@ void launchStartPosCheck(const DTables* T, int P, const coffee_start_position* s
 void launchSelfplayInit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
   hipLaunchKernelGGL(kInit, dim3(d.G), dim3(64), 0, st, dd, d.T);
   KC_HIP(hipGetLastError());
+  if(d.matchMode && d.matchPerSide) {
+    hipLaunchKernelGGL(kMatchSideLimits, dim3((d.G + 255) / 256), dim3(256), 0, st, dd);
+    KC_HIP(hipGetLastError());
+  }
   if(d.analysisMode) {
     hipLaunchKernelGGL(kAnalysisInit, dim3((d.G + 255) / 256), dim3(256), 0, st, dd);
     KC_HIP(hipGetLastError());
@@ -4658,6 +4731,8 @@ void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
 void launchGameTree(const SearchDev* dd, int slot, int maxNodes, uint32_t* nodesOut, uint32_t* edgesOut,
                     int32_t* count, hipStream_t st) {
   hipLaunchKernelGGL(kGameTree, dim3(1), dim3(64), 0, st, dd, slot, maxNodes, nodesOut, edgesOut, count);
+  KC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(kGameTreeSides, dim3(1), dim3(64), 0, st, dd, slot, maxNodes, nodesOut, edgesOut, count);
   KC_HIP(hipGetLastError());
 }
 

@@ -136,9 +136,65 @@ void validateMatchConfig(const coffee_match_config& c) {
   reject(sp.value_surprise_data_weight != 0.0f, "value_surprise_data_weight", rows);
 }
 
+int nodeCapFor(int nodeCap, int maxVisits) {
+  const int cap = nodeCap > 0 ? nodeCap : std::max(2048, 3 * maxVisits);
+  return (cap + 63) / 64 * 64;
+}
+
+void validateMatchOptions(const coffee_match_config& c, const coffee_match_options* o) {
+  if(!o)
+    return;
+  if((o->per_side != 0 && o->per_side != 1) || (o->share_net != 0 && o->share_net != 1))
+    throw std::invalid_argument("match options: per_side and share_net must be 0 or 1");
+  if(o->share_net) {
+    const char *a = c.model_path[0], *b = c.model_path[1];
+    if((a == nullptr) != (b == nullptr) || (a && strcmp(a, b) != 0))
+      throw std::invalid_argument("match options: share_net needs equal model_path[0] and model_path[1]");
+  }
+  if(!o->per_side)
+    return;
+  int maxVisits = 0;
+  for(int i = 0; i < 2; i++) {
+    const std::string side = "match options: side " + std::to_string(i) + ": ";
+    const coffee_search_params& sp = o->side[i].search;
+    try {
+      coffee_match_config t = c;
+      t.search = sp;
+      validateMatchConfig(t);
+      if(sp.max_visits < 1)
+        throw std::invalid_argument("max_visits must be >= 1");
+      if(sp.root_num_symmetries_to_sample < 1 || sp.root_num_symmetries_to_sample > 4)
+        throw std::invalid_argument("root_num_symmetries_to_sample must be in 1..4");
+      try {
+        toUnc(o->side[i].unc);
+      } catch(const std::invalid_argument& e) {
+        throw std::invalid_argument(std::string("unc: ") + e.what());
+      }
+      // game-level settings are one per engine (bit patterns: a NaN equals itself here)
+      if(sp.init_games_with_policy != c.search.init_games_with_policy)
+        throw std::invalid_argument("init_games_with_policy must equal the config's search (a game-level setting)");
+      if(memcmp(&sp.policy_init_area_prop, &c.search.policy_init_area_prop, sizeof(float)) != 0)
+        throw std::invalid_argument("policy_init_area_prop must equal the config's search (a game-level setting)");
+      if(memcmp(&sp.policy_init_area_temperature, &c.search.policy_init_area_temperature, sizeof(float)) != 0)
+        throw std::invalid_argument(
+            "policy_init_area_temperature must equal the config's search (a game-level setting)");
+    } catch(const std::invalid_argument& e) {
+      throw std::invalid_argument(side + e.what());
+    }
+    maxVisits = std::max(maxVisits, sp.max_visits);
+  }
+  // the engine's rule for cfg->search.max_visits, on each side (the default pool comes from the larger)
+  const int cap = nodeCapFor(c.node_cap, maxVisits);
+  for(int i = 0; i < 2; i++)
+    if(cap < o->side[i].search.max_visits + 4)
+      throw std::invalid_argument("match options: side " + std::to_string(i) +
+                                  ": max_visits: node_cap must exceed max_visits + 3");
+}
+
 // The self-play config a match engine is built on: one row of row buffer (never written).
-coffee_selfplay_config SelfplayEngine::matchBase(const coffee_match_config& c) {
+coffee_selfplay_config SelfplayEngine::matchBase(const coffee_match_config& c, const coffee_match_options* o) {
   validateMatchConfig(c);  // before the first HIP call
+  validateMatchOptions(c, o);
   coffee_selfplay_config b;
   memset(&b, 0, sizeof(b));
   b.x = c.x;
@@ -160,7 +216,8 @@ coffee_selfplay_config SelfplayEngine::matchBase(const coffee_match_config& c) {
   return b;
 }
 
-SelfplayEngine::SelfplayEngine(const coffee_match_config& c) : SelfplayEngine(matchBase(c), c.model_path) {}
+SelfplayEngine::SelfplayEngine(const coffee_match_config& c, const coffee_match_options* opts)
+    : SelfplayEngine(matchBase(c, opts), c.model_path, opts) {}
 
 // The settings analysis rejects: a query is one search from a cleared tree, and nothing is
 // played or recorded, so every setting that keeps a tree, makes rows or plays opening moves
@@ -250,7 +307,10 @@ SelfplayEngine::SelfplayEngine(const coffee_analysis_config& c) : SelfplayEngine
   KC_HIP(hipStreamSynchronize(stream_));
 }
 
-SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* const* matchPaths) {
+SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* const* matchPaths,
+                               const coffee_match_options* matchOpts) {
+  const bool perSide = matchPaths && matchOpts && matchOpts->per_side;
+  const bool sharedNet = matchPaths && matchOpts && matchOpts->share_net;
   if(c.num_games <= 0)
     throw std::invalid_argument("num_games must be positive");
   if(c.num_games > 65535)  // kCompact packs two per-device game counts into 16-bit halves
@@ -289,18 +349,21 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* cons
   const DTables& ht = hostTables(c.x, c.y, c.win_len);
   T_ = deviceTables(c.x, c.y, c.win_len);
   commitInterval_ = c.commit_interval > 0 ? c.commit_interval : 8;
-  int cap = c.node_cap > 0 ? c.node_cap : std::max(2048, 3 * sp.max_visits);
-  cap = (cap + 63) / 64 * 64;
+  // (per-side match settings: the default pool serves the larger side; validateMatchOptions
+  // checked each side's max_visits against it)
+  const int cap = nodeCapFor(c.node_cap, perSide ? std::max(matchOpts->side[0].search.max_visits,
+                                                            matchOpts->side[1].search.max_visits)
+                                                 : sp.max_visits);
   if(cap > 65535)
     throw std::invalid_argument("node_cap must be <= 65535");
-  if(cap < sp.max_visits + 4)
+  if(!perSide && cap < sp.max_visits + 4)  // (per side: validateMatchOptions)
     throw std::invalid_argument("node_cap must exceed max_visits + 3");
   const int G = c.num_games, P = ht.P, A = ht.A;
   const int ttCap = nextPow2(2 * cap);
   const int rowCap = c.row_capacity > 0 ? c.row_capacity : 4 * G * A;
   if(matchPaths) {
-    numNets_ = 2;
-    for(int n = 0; n < 2; n++)
+    numNets_ = sharedNet ? 1 : 2;  // a shared net: one instance evaluates both sides
+    for(int n = 0; n < numNets_; n++)
       if(matchPaths[n]) {
         nets_[n].model.reset(new ModelHost(loadModel(matchPaths[n])));
         nets_[n].nn.reset(new NNEngine(*nets_[n].model, c.x, c.y, c.win_len, c.nn_precision));
@@ -405,7 +468,7 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* cons
     d.cVal = devAlloc<float>(owned_, entries * 2, false);
     d.cErr = devAlloc<float>(owned_, entries, false);
     d.cTag = devAlloc<uint32_t>(owned_, entries);
-    if(matchPaths) {  // net 1's own cache
+    if(matchPaths && !sharedNet) {  // net 1's own cache
       d.cKey1 = devAlloc<uint64_t>(owned_, entries * 2);
       d.cPol1 = devAlloc<float>(owned_, entries * P, false);
       d.cVal1 = devAlloc<float>(owned_, entries * 2, false);
@@ -419,11 +482,22 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* cons
     d.nnCount1 = devAlloc<int32_t>(owned_, 1);
     d.nnPeak = devAlloc<int32_t>(owned_, 2);
     d.nnNetEvals = devAlloc<unsigned long long>(owned_, 2);
+    d.matchSharedNet = sharedNet ? 1 : 0;
   }
   {
     coffee_uncertainty_params u;
     coffee_uncertainty_params_default(&u);
     d.unc = toUnc(u);  // off
+    d.unc1 = d.unc;
+  }
+  d.sp1 = d.sp;
+  if(perSide) {
+    d.matchPerSide = 1;
+    d.sp = toSP(matchOpts->side[0].search);
+    d.spCheap = cheapSearchSP(d.sp);
+    d.sp1 = toSP(matchOpts->side[1].search);
+    d.unc = toUnc(matchOpts->side[0].unc);
+    d.unc1 = toUnc(matchOpts->side[1].unc);
   }
   d.cClear = devAlloc<uint32_t>(owned_, G);
   d.pendList = devAlloc<int32_t>(owned_, G, false);
@@ -567,7 +641,8 @@ void SelfplayEngine::step(int rounds, hipStream_t st) {
     launchCompact(d, dd_, st, t1, selected && resolveInCompact_);
     timedKernel(1, t1, [&](hipEvent_t a, hipEvent_t b) { forwardNet(0, d.nnCount, d.nnIdx, st, a, b); });
     // match play: net 1's list in its own launch, after net 0's on the same stream
-    if(d.matchMode)
+    // (a shared net evaluates both sides' rows in the launch above)
+    if(d.matchMode && !d.matchSharedNet)
       forwardNet(1, d.nnCount1, d.nnIdx1, st, nullptr, nullptr);
     const bool commitNow = (rounds_ + 1) % (uint64_t)commitInterval_ == 0 || r == rounds - 1;
     if(fuse && !commitNow) {
@@ -590,6 +665,8 @@ void SelfplayEngine::step(int rounds, hipStream_t st) {
 
 void SelfplayEngine::setUncertainty(const coffee_uncertainty_params& p) {
   const Unc u = toUnc(p);
+  if(hd_.matchPerSide)
+    throw std::invalid_argument("set_uncertainty: the match engine's sides carry their own (coffee_match_options)");
   // a tree must never mix the two rules: only before the first round, and in analysis before
   // the first query (a step loads the queued queries, also one of zero rounds)
   if(rounds_ > 0 || aSubmitted_ > 0)

@@ -26,6 +26,13 @@ void checkStartPositions(int x, int y, int winLen, int n, const coffee_start_pos
 // the offending setting): geometry, and the settings match play rejects because they keep
 // a tree across moves or exist only to make training rows.
 void validateMatchConfig(const coffee_match_config& c);
+// The same for the per-side options of coffee_match_create2 (nullptr: nothing to check): each
+// side's parameters as validateMatchConfig and the engine's own range checks see them, its
+// uncertainty parameters, the game-level fields against c.search, share_net's equal model
+// paths, and the node pool against each side's max_visits.  The message names side and field.
+void validateMatchOptions(const coffee_match_config& c, const coffee_match_options* o);
+// The node pool of a config: node_cap (0: max(2048, 3 * maxVisits)) rounded up to 64.
+int nodeCapFor(int nodeCap, int maxVisits);
 // The same for an analysis config: geometry, num_slots, query_capacity, max_pv_len, and the
 // settings of validateMatchConfig plus init_games_with_policy.
 void validateAnalysisConfig(const coffee_analysis_config& c);
@@ -37,7 +44,8 @@ class SelfplayEngine {
  public:
   explicit SelfplayEngine(const coffee_selfplay_config& c) : SelfplayEngine(c, nullptr) {}
   // Match mode: net 0 (baseline) against net 1 (candidate); a NULL model path is the stand-in
-  explicit SelfplayEngine(const coffee_match_config& c);
+  // opts (coffee_match_create2; nullptr: none): per-side search settings, one shared net
+  explicit SelfplayEngine(const coffee_match_config& c, const coffee_match_options* opts = nullptr);
   // Analysis mode (DESIGN.md "Analysis"): the slots search queued positions instead of games
   explicit SelfplayEngine(const coffee_analysis_config& c);
   ~SelfplayEngine();
@@ -97,9 +105,10 @@ class SelfplayEngine {
   void resolveTiming();
   std::vector<PendingTiming> pending_;
   std::vector<hipEvent_t> evPool_;
-  // matchPaths: the two model paths of match mode (self-play: nullptr)
-  SelfplayEngine(const coffee_selfplay_config& c, const char* const* matchPaths);
-  static coffee_selfplay_config matchBase(const coffee_match_config& c);
+  // matchPaths: the two model paths of match mode (self-play: nullptr); matchOpts: its options
+  SelfplayEngine(const coffee_selfplay_config& c, const char* const* matchPaths,
+                 const coffee_match_options* matchOpts = nullptr);
+  static coffee_selfplay_config matchBase(const coffee_match_config& c, const coffee_match_options* o);
   static coffee_selfplay_config analysisBase(const coffee_analysis_config& c);
   // analysis: queries submitted / results drained so far
   uint64_t aSubmitted_ = 0, aDrained_ = 0;

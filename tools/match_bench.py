@@ -3,6 +3,7 @@
 
   python tools/match_bench.py [--arch b6c96] [--games 1024] [--visits 150] [--rounds 3000]
                               [--warmup 600] [--precision default] [--repeats 3]
+                              [--equal-sides] [--share-net]
 
 Two seeded random nets of one architecture play each other on one kc.Match engine; a
 kc.Selfplay engine with the same net, games, visits, search parameters, commit interval
@@ -11,7 +12,11 @@ and cache runs the same number of rounds for comparison.  Each figure is the med
 that ends in a device synchronise.  Prints one JSON line.  What the comparison says: a
 match round runs two network launches (one per net, one after the other) where self-play
 runs one, and never fuses backup and select; the difference in time per round is the
-price of both, and the bound on what overlapping the two launches could win back."""
+price of both, and the bound on what overlapping the two launches could win back.
+--equal-sides runs the match with per-side settings, both sides the engine's own (the
+per-side code path at unchanged results); --share-net plays one net against itself on one
+network instance -- one launch a round, one cache -- which wins the second
+launch back."""
 import argparse
 import json
 import os
@@ -52,6 +57,10 @@ def main():
     ap.add_argument("--cache-log2", type=int, default=21)
     ap.add_argument("--uncertainty", action="store_true",
                     help="uncertainty weighting on (set_uncertainty(use_uncertainty=1), default values) in both engines")
+    ap.add_argument("--equal-sides", action="store_true",
+                    help="per-side settings with both sides the engine's own parameters (kc.Match(sides=...))")
+    ap.add_argument("--share-net", action="store_true",
+                    help="one net on both sides, one network instance and launch (kc.Match(share_net=True))")
     a = ap.parse_args()
     X, Y, W = 5, 5, 4
     search = kc.default_match_params(max_visits=a.visits)
@@ -62,8 +71,16 @@ def main():
             kc.write_random_model(a.arch, 1000 + i, p)
         common = dict(num_games=a.games, seed=7, commit_interval=16, nn_cache_log2=a.cache_log2,
                       nn_precision=a.precision, start_stagger=a.visits)
-        m = kc.Match(X, Y, W, baseline_path=paths[0], candidate_path=paths[1], search=search, **common)
-        m.set_uncertainty(use_uncertainty=int(a.uncertainty))
+        extra = {}
+        if a.equal_sides:
+            unc = kc.default_uncertainty_params(use_uncertainty=int(a.uncertainty))
+            extra["sides"] = ((search, unc), (search, unc))
+        if a.share_net:
+            extra["share_net"] = True
+        m = kc.Match(X, Y, W, baseline_path=paths[0], candidate_path=paths[0 if a.share_net else 1], search=search,
+                     **common, **extra)
+        if not a.equal_sides:  # (the sides carry their own)
+            m.set_uncertainty(use_uncertainty=int(a.uncertainty))
         msecs, mgames, mst = timed(m, a.rounds, a.warmup, a.repeats, m.drain_games)
         m.close()
         over.pop("max_visits")
@@ -80,6 +97,7 @@ def main():
     print(json.dumps({
         "arch": a.arch, "geometry": [X, Y, W], "games": a.games, "visits": a.visits, "precision": a.precision,
         "rounds_per_window": a.rounds, "windows": a.repeats, "uncertainty": bool(a.uncertainty),
+        "equal_sides": bool(a.equal_sides), "share_net": bool(a.share_net),
         "match": {"games_per_s": round(mgames, 2), "rounds_per_s": round(a.rounds / med_m, 1),
                   "us_per_round": round(1e6 * med_m / a.rounds, 2), "window_s": [round(x, 4) for x in msecs],
                   "nn_evals": mst["nn_evals"], "nn_batch_peak": mst["nn_batch_peak"],
