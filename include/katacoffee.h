@@ -447,7 +447,8 @@ enum {
   COFFEE_ANALYSIS_OK = 0,            /* searched: the move records are valid */
   COFFEE_ANALYSIS_ILLEGAL_MOVE = 1,  /* info = index of the first illegal move */
   COFFEE_ANALYSIS_GAME_OVER = 2,     /* the move list ends the game: info = winner (0 draw: board full) */
-  COFFEE_ANALYSIS_NO_LEGAL_MOVE = 3  /* the side to move has no legal move (a draw) */
+  COFFEE_ANALYSIS_NO_LEGAL_MOVE = 3, /* the side to move has no legal move (a draw) */
+  COFFEE_ANALYSIS_NO_ALLOWED_MOVE = 4 /* the query's avoid / allow set leaves no legal move (root restrictions below) */
 };
 
 typedef struct coffee_analysis_config {
@@ -539,6 +540,62 @@ int coffee_analysis_game_info(coffee_analysis* h, int slot, int64_t* info);
 int coffee_analysis_game_tree(coffee_analysis* h, int slot, int max_nodes, uint32_t* nodes, uint32_t* edges,
                               int* n_nodes);
 int coffee_analysis_root_policy(coffee_analysis* h, int slot, float* out);
+
+/* ---- root move restrictions of analysis (the reference's rootSymmetryPruning,
+ *      setup.cpp:639-644, and allowMoves / avoidMoves, analysis.cpp:1030-1097) ----
+ * A query's search treats a set of root moves as unavailable, its mask:
+ *   root symmetries: s in 0..7 (bit 0 flips y, bit 1 flips x, bit 2 transposes; x != y: 0..3)
+ *     under which the packed V1 input of the root position equals the identity's bit for bit;
+ *   image of move d*A + c under s: symDir[s][d]*A + symCell[s][c] (coffee_symmetry_move);
+ *   avoid set: the query's bits (mode 1), or the complement of its bits (mode 2, allow);
+ *   used symmetries: the root symmetries that map the avoid set onto itself (a group);
+ *   pruned (root_symmetry_pruning on): a legal, not avoided move with an image under a used
+ *     symmetry at a lower position -- the survivor of each orbit is its lowest position;
+ *   mask = avoid set + pruned set.
+ * The masked moves' entries of the root's noised policy (coffee_analysis_root_policy) are -1,
+ * so the root never expands them; noise and temperature are drawn over all legal moves first,
+ * so the other entries and the RNG stream are what they are without a mask.  A query whose mask
+ * leaves no legal move is answered at once with COFFEE_ANALYSIS_NO_ALLOWED_MOVE. */
+typedef struct coffee_analysis_root_options {
+  int32_t root_symmetry_pruning; /* 0 */
+  int32_t include_policy;        /* 0; 1: coffee_analysis_drain2 fills policy_out */
+} coffee_analysis_root_options;
+#define COFFEE_ANALYSIS_RESTRICT_WORDS 11
+typedef struct coffee_analysis_restrict {  /* one per query, beside it */
+  uint32_t avoid[COFFEE_ANALYSIS_RESTRICT_WORDS]; /* bit p of word p / 32: policy position p */
+  int32_t mode;                  /* 0 none (bits ignored), 1 avoid the set, 2 allow only the set */
+} coffee_analysis_restrict;
+typedef struct coffee_analysis_root_info {  /* one per result, beside it */
+  uint32_t symmetries;           /* bit s: symmetry s was used (status 0 and 4; else 0) */
+  int32_t num_masked;            /* legal root moves in the mask */
+} coffee_analysis_root_info;
+/* Engine-wide; only before the first submitted query (COFFEE_EINVAL afterwards or for a value
+ * other than 0 / 1), like coffee_analysis_set_uncertainty. */
+int coffee_analysis_set_root_options(coffee_analysis* h, const coffee_analysis_root_options* opts);
+/* coffee_analysis_submit with restrict_in [n] (host; NULL: no query is restricted).  A mode
+ * outside 0..2, a set bit at a position >= 4*x*y, or a mode other than 0 on a board with more
+ * than 352 positions fails the call with COFFEE_EINVAL and submits nothing. */
+int coffee_analysis_submit2(coffee_analysis* h, const coffee_analysis_query* queries,
+                            const coffee_analysis_restrict* restrict_in, int n, int* accepted);
+/* coffee_analysis_drain that also fills root_out [max] (NULL: skipped) and, on an engine with
+ * include_policy, policy_out [max][4*x*y] (NULL: skipped): the root's network policy before
+ * temperature, noise and mask, -1 at illegal moves; zeros for a result without a search.
+ * policy_out on an engine without include_policy is COFFEE_EINVAL. */
+int coffee_analysis_drain2(coffee_analysis* h, int max, coffee_analysis_result* header_out,
+                           coffee_analysis_move* moves_out, coffee_analysis_root_info* root_out,
+                           float* policy_out, int* n_out);
+/* The rule on the host (no engine, no device), the code the kernels run.  colours [x*y] 0 / 1 /
+ * 2; hist_cell / hist_dir [n_hist <= 5]: the last moves, most recent first; legal_bits
+ * [ceil(4xy/32)] words; avoid_bits [11] words with mode as in coffee_analysis_restrict (mode 0:
+ * may be NULL); prune 0 / 1.  mask_out [ceil(4xy/32)] words, *syms_out the used symmetries.
+ * Returns the number of legal moves left unmasked (0: the query would be answered with
+ * COFFEE_ANALYSIS_NO_ALLOWED_MOVE, or the position has no legal move), or a COFFEE_E* code. */
+int coffee_root_mask(int x, int y, int win_len, const uint8_t* colours, const int32_t* hist_cell,
+                     const int32_t* hist_dir, int n_hist, const uint32_t* legal_bits, const uint32_t* avoid_bits,
+                     int mode, int prune, uint32_t* mask_out, uint32_t* syms_out);
+/* The image of policy position `move` under symmetry `sym` (0..7) on an x * y board, or
+ * COFFEE_EINVAL. */
+int coffee_symmetry_move(int x, int y, int sym, int move);
 
 /* ---- uncertainty weighting of playouts (the reference's useUncertainty) ----
  * An evaluation whose short-term win/loss error the net predicts to be large counts for less

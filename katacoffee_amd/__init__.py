@@ -185,8 +185,20 @@ ANALYSIS_MOVE = np.dtype([("move", np.int32), ("edge_visits", np.uint32), ("visi
                           ("prior", np.float32), ("lcb", np.float32), ("radius", np.float32),
                           ("play_selection_value", np.float32), ("order", np.int32), ("pv_len", np.int32),
                           ("pv", np.uint16, (ANALYSIS_MAX_PV,))], align=True)
+# coffee_analysis_restrict / _root_info (root restrictions)
+ANALYSIS_NO_ALLOWED_MOVE = 4
+ANALYSIS_RESTRICT_WORDS = 11
+ANALYSIS_RESTRICT = np.dtype([("avoid", np.uint32, (ANALYSIS_RESTRICT_WORDS,)), ("mode", np.int32)], align=True)
+ANALYSIS_ROOT_INFO = np.dtype([("symmetries", np.uint32), ("num_masked", np.int32)], align=True)
+assert ANALYSIS_RESTRICT.itemsize == 48 and ANALYSIS_ROOT_INFO.itemsize == 8
+
+
+class AnalysisRootOptions(ctypes.Structure):
+    _fields_ = [("root_symmetry_pruning", ctypes.c_int32), ("include_policy", ctypes.c_int32)]
+
+
 # coffee_start_position
-START_POSITION = np.dtype([("weight", np.float32), ("num_moves", np.int32),
+START_POSITION =np.dtype([("weight", np.float32), ("num_moves", np.int32),
                            ("moves", np.uint16, (ANALYSIS_MAX_MOVES,))], align=True)
 assert START_POSITION.itemsize == 208
 assert ANALYSIS_QUERY.itemsize == 232 and ANALYSIS_RESULT.itemsize == 56 and ANALYSIS_MOVE.itemsize == 80
@@ -219,6 +231,8 @@ EXPORTS = [
     "coffee_start_position_pick", "coffee_start_position_draws", "coffee_start_position_index", "coffee_selfplay_set_start_positions",
     "coffee_match_set_start_positions", "coffee_selfplay_start_position_games", "coffee_match_start_position_games",
     "coffee_match_create2", "coffee_match_elo",
+    "coffee_analysis_set_root_options", "coffee_analysis_submit2", "coffee_analysis_drain2", "coffee_root_mask",
+    "coffee_symmetry_move",
 ]
 
 
@@ -332,6 +346,12 @@ def lib():
         if hasattr(L, "coffee_match_create2"):  # (absent in earlier builds run as A/B references)
             L.coffee_match_create2.argtypes = [c_p, c_p, c_p]
             L.coffee_match_elo.argtypes = [ctypes.c_int64] * 3 + [c_p] * 5
+        if hasattr(L, "coffee_root_mask"):  # (absent in earlier builds run as A/B references)
+            L.coffee_analysis_set_root_options.argtypes = [c_p, c_p]
+            L.coffee_analysis_submit2.argtypes = [c_p, c_p, c_p, c_i, c_p]
+            L.coffee_analysis_drain2.argtypes = [c_p, c_i, c_p, c_p, c_p, c_p, c_p]
+            L.coffee_root_mask.argtypes = [c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p]
+            L.coffee_symmetry_move.argtypes = [c_i, c_i, c_i, c_i]
         _lib = L
     return _lib
 
@@ -502,6 +522,78 @@ def analysis_queries(queries):
         out[i]["num_moves"] = len(moves)
         out[i]["moves"][:len(moves)] = moves
     return out
+
+
+def move_bits(moves, words):
+    """Policy positions as a bit set of `words` uint32 words (bit p of word p // 32)."""
+    out = np.zeros(words, np.uint32)
+    for m in moves:
+        m = int(m)
+        if not 0 <= m < 32 * words:
+            raise CoffeeError("move %d does not fit a set of %d words" % (m, words))
+        out[m >> 5] |= np.uint32(1 << (m & 31))
+    return out
+
+
+def analysis_restricts(queries, P):
+    """The root restrictions of query dicts as an ANALYSIS_RESTRICT array, or None when no query
+    carries one (or queries is a structured array).  A query's `avoid_moves` / `allow_moves` are
+    lists of policy positions; giving both is an error."""
+    if isinstance(queries, np.ndarray) or not any("avoid_moves" in q or "allow_moves" in q for q in queries):
+        return None
+    out = np.zeros(len(queries), ANALYSIS_RESTRICT)
+    for i, q in enumerate(queries):
+        if "avoid_moves" in q and "allow_moves" in q:
+            raise CoffeeError("query %r: avoid_moves and allow_moves are exclusive" % (q.get("id"),))
+        for key, mode in (("avoid_moves", 1), ("allow_moves", 2)):
+            if key in q:
+                out[i]["avoid"] = move_bits(q[key], ANALYSIS_RESTRICT_WORDS)
+                out[i]["mode"] = mode
+    return out
+
+
+def symmetry_move(X, Y, sym, move):
+    """The image of policy position `move` under symmetry `sym` (coffee_symmetry_move; host)."""
+    rc = lib().coffee_symmetry_move(X, Y, sym, move)
+    if rc < 0:
+        check(rc)
+    return rc
+
+
+def root_mask(X, Y, W, colours, hist_cell, hist_dir, legal, avoid_moves=None, allow_moves=None, prune=True,
+              avoid_bits=None, mode=None):
+    """The root restriction rule on the host (coffee_root_mask; no device): a dict with `mask`
+    (bool [P]), `symmetries` (the used ones, a sorted list), `bits` (the same as a bit set),
+    `num_masked` (masked legal moves) and `left` (legal moves left unmasked; 0 is the engine's
+    NO_ALLOWED_MOVE answer).  colours [A] 0 / 1 / 2; hist_cell / hist_dir: the last moves, most
+    recent first (at most five); legal: bool [P].  avoid_bits / mode pass raw words instead of a
+    move list."""
+    A, P = X * Y, 4 * X * Y
+    nw = (P + 31) // 32
+    if avoid_moves is not None and allow_moves is not None:
+        raise CoffeeError("root_mask: avoid_moves and allow_moves are exclusive")
+    if avoid_bits is None:
+        mode = 1 if avoid_moves is not None else (2 if allow_moves is not None else 0)
+        lst = avoid_moves if avoid_moves is not None else (allow_moves if allow_moves is not None else [])
+        avoid_bits = move_bits(lst, ANALYSIS_RESTRICT_WORDS)
+    avoid_bits = np.ascontiguousarray(avoid_bits, np.uint32)
+    col = np.ascontiguousarray(colours, np.uint8).reshape(A)
+    hc = np.ascontiguousarray(hist_cell, np.int32)
+    hd = np.ascontiguousarray(hist_dir, np.int32)
+    lg = np.ascontiguousarray(legal).astype(bool).reshape(P)
+    legal_bits = np.zeros(nw, np.uint32)
+    for p in np.nonzero(lg)[0]:
+        legal_bits[p >> 5] |= np.uint32(1 << (int(p) & 31))
+    mask = np.zeros(nw, np.uint32)
+    syms = ctypes.c_uint32()
+    rc = lib().coffee_root_mask(X, Y, W, _ptr(col), _ptr(hc) if len(hc) else None, _ptr(hd) if len(hd) else None,
+                                len(hc), _ptr(legal_bits), _ptr(avoid_bits), int(mode), int(bool(prune)), _ptr(mask),
+                                ctypes.byref(syms))
+    if rc < 0:
+        check(rc)
+    m = np.array([(int(mask[p >> 5]) >> (p & 31)) & 1 for p in range(P)], bool)
+    return {"mask": m, "symmetries": [s for s in range(8) if (syms.value >> s) & 1], "bits": syms.value,
+            "num_masked": int((m & lg).sum()), "left": rc}
 
 
 def analysis_query_check(X, Y, W, query):
@@ -1092,8 +1184,10 @@ class Analysis:
 
     def __init__(self, X=5, Y=5, W=4, num_slots=64, model_path=None, search=None, seed=1, node_cap=0,
                  commit_interval=0, nn_cache_log2=0, nn_batch_cap=0, nn_precision="default", engines_per_device=0,
-                 query_capacity=0, max_pv_len=ANALYSIS_MAX_PV, **search_over):
+                 query_capacity=0, max_pv_len=ANALYSIS_MAX_PV, root_symmetry_pruning=False, include_policy=False,
+                 **search_over):
         self.X, self.Y, self.W = X, Y, W
+        self.root_symmetry_pruning, self.include_policy = False, False
         self.A, self.P = X * Y, 4 * X * Y
         self.num_slots = num_slots
         search = default_analysis_params() if search is None else SearchParams.from_buffer_copy(search)
@@ -1118,14 +1212,37 @@ class Analysis:
         self.cfg = cfg
         self.h = ctypes.c_void_p()
         check(lib().coffee_analysis_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+        if root_symmetry_pruning or include_policy:
+            self.set_root_options(root_symmetry_pruning, include_policy)
 
-    def submit(self, queries):
+    def submit(self, queries, restricts=None):
         """Queues queries; returns how many were accepted (the first ones): submitted minus
-        drained never exceeds query_capacity."""
+        drained never exceeds query_capacity.  A query dict's `avoid_moves` / `allow_moves` (or
+        restricts, an ANALYSIS_RESTRICT array beside a query array) restrict its root; such
+        queries go through coffee_analysis_submit2, others through coffee_analysis_submit."""
         q = analysis_queries(queries)
+        r = analysis_restricts(queries, self.P) if restricts is None else np.ascontiguousarray(restricts)
+        if r is None:
+            n = ctypes.c_int()
+            check(lib().coffee_analysis_submit(self.h, _ptr(q), len(q), ctypes.byref(n)))
+            return n.value
+        return self.submit2(q, r)
+
+    def submit2(self, queries, restricts=None):
+        """submit() through coffee_analysis_submit2 whether or not a query is restricted."""
+        q = analysis_queries(queries)
+        r = analysis_restricts(queries, self.P) if restricts is None else np.ascontiguousarray(restricts)
+        if r is not None and (r.dtype != ANALYSIS_RESTRICT or len(r) != len(q)):
+            raise CoffeeError("restricts: one ANALYSIS_RESTRICT entry per query")
         n = ctypes.c_int()
-        check(lib().coffee_analysis_submit(self.h, _ptr(q), len(q), ctypes.byref(n)))
+        check(lib().coffee_analysis_submit2(self.h, _ptr(q), None if r is None else _ptr(r), len(q), ctypes.byref(n)))
         return n.value
+
+    def set_root_options(self, root_symmetry_pruning=False, include_policy=False):
+        """coffee_analysis_set_root_options; only before the first submitted query."""
+        o = AnalysisRootOptions(int(root_symmetry_pruning), int(include_policy))
+        check(lib().coffee_analysis_set_root_options(self.h, ctypes.byref(o)))
+        self.root_symmetry_pruning, self.include_policy = bool(root_symmetry_pruning), bool(include_policy)
 
     def step(self, rounds, stream=None):
         check(lib().coffee_analysis_step(self.h, rounds, stream))
@@ -1140,39 +1257,60 @@ class Analysis:
     def sync(self):
         check(lib().coffee_analysis_sync(self.h))
 
-    def drain(self, max_results=None):
-        """(headers [n], moves [n][P]) of the finished results, in completion order."""
+    def drain(self, max_results=None, with_root=False):
+        """(headers [n], moves [n][P]) of the finished results, in completion order.  with_root:
+        (headers, moves, root, policy) through coffee_analysis_drain2 -- root [n]
+        (ANALYSIS_ROOT_INFO: `symmetries` bits and `num_masked`), policy [n][P] on an engine
+        with include_policy (else None)."""
         cap = self.query_capacity if max_results is None else min(max_results, self.query_capacity)
         header = np.zeros(cap, ANALYSIS_RESULT)
         moves = np.zeros((cap, self.P), ANALYSIS_MOVE)
         n = ctypes.c_int()
-        check(lib().coffee_analysis_drain(self.h, cap, _ptr(header), _ptr(moves), ctypes.byref(n)))
-        return header[:n.value], moves[:n.value]
+        if not with_root:
+            check(lib().coffee_analysis_drain(self.h, cap, _ptr(header), _ptr(moves), ctypes.byref(n)))
+            return header[:n.value], moves[:n.value]
+        root = np.zeros(cap, ANALYSIS_ROOT_INFO)
+        policy = np.zeros((cap, self.P), np.float32) if self.include_policy else None
+        check(lib().coffee_analysis_drain2(self.h, cap, _ptr(header), _ptr(moves), _ptr(root),
+                                           None if policy is None else _ptr(policy), ctypes.byref(n)))
+        return header[:n.value], moves[:n.value], root[:n.value], None if policy is None else policy[:n.value]
 
-    def analyze(self, queries, rounds_per_step=32, max_steps=1 << 20):
+    def drain2(self, max_results=None):
+        return self.drain(max_results, with_root=True)
+
+    def analyze(self, queries, rounds_per_step=32, max_steps=1 << 20, with_root=False):
         """Submits every query (as capacity allows), steps and drains until each id is back;
-        returns (headers, moves) in the order of `queries`.  The ids must be distinct."""
+        returns (headers, moves) in the order of `queries`, with_root (headers, moves, root,
+        policy) as drain() does.  The ids must be distinct."""
         q = analysis_queries(queries)
+        r = analysis_restricts(queries, self.P)
         ids = [int(i) for i in q["id"]]
         if len(set(ids)) != len(ids):
             raise CoffeeError("analyze: query ids must be distinct")
-        sent, got = 0, {}
+        sent, got, want = 0, {}, set(ids)
         for _ in range(max_steps):
             if len(got) == len(ids):
                 break
             if sent < len(q):
-                sent += self.submit(q[sent:])
+                sent += self.submit(q[sent:], None if r is None else r[sent:])
             self.step(rounds_per_step)
-            h, m = self.drain()
-            for i in range(len(h)):
-                got[int(h[i]["id"])] = (h[i].copy(), m[i].copy())
+            res = self.drain(with_root=with_root)
+            for i in range(len(res[0])):
+                if int(res[0][i]["id"]) in want:  # (results of queries submitted before this call are dropped)
+                    got[int(res[0][i]["id"])] = tuple(None if a is None else a[i].copy() for a in res)
         else:
             raise CoffeeError("analyze: the queries did not finish")
         header = np.zeros(len(ids), ANALYSIS_RESULT)
         moves = np.zeros((len(ids), self.P), ANALYSIS_MOVE)
+        root = np.zeros(len(ids), ANALYSIS_ROOT_INFO)
+        policy = np.zeros((len(ids), self.P), np.float32) if with_root and self.include_policy else None
         for k, i in enumerate(ids):
-            header[k], moves[k] = got[i]
-        return header, moves
+            header[k], moves[k] = got[i][0], got[i][1]
+            if with_root:
+                root[k] = got[i][2]
+                if policy is not None:
+                    policy[k] = got[i][3]
+        return (header, moves, root, policy) if with_root else (header, moves)
 
     def stats(self):
         s = AnalysisStats()

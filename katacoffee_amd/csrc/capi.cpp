@@ -679,7 +679,7 @@ int coffee_analysis_submit(coffee_analysis* h, const coffee_analysis_query* quer
     need(h && h->eng && accepted, "NULL argument");
     need(n >= 0 && (n == 0 || queries), "n must be >= 0 and queries non-NULL");
     *accepted = 0;
-    *accepted = h->eng->analysisSubmit(queries, n);
+    *accepted = h->eng->analysisSubmit(queries, nullptr, n);
   });
 }
 
@@ -690,6 +690,98 @@ int coffee_analysis_drain(coffee_analysis* h, int max, coffee_analysis_result* h
     need(max >= 0, "max must be >= 0");
     *n_out = h->eng->analysisDrain(max, header_out, moves_out);
   });
+}
+
+int coffee_analysis_set_root_options(coffee_analysis* h, const coffee_analysis_root_options* opts) {
+  return guarded([&] {
+    need(h && h->eng && opts, "NULL argument");
+    h->eng->setRootOptions(*opts);
+  });
+}
+
+int coffee_analysis_submit2(coffee_analysis* h, const coffee_analysis_query* queries,
+                            const coffee_analysis_restrict* restrict_in, int n, int* accepted) {
+  return guarded([&] {
+    need(h && h->eng && accepted, "NULL argument");
+    need(n >= 0 && (n == 0 || queries), "n must be >= 0 and queries non-NULL");
+    *accepted = 0;
+    *accepted = h->eng->analysisSubmit(queries, restrict_in, n);
+  });
+}
+
+int coffee_analysis_drain2(coffee_analysis* h, int max, coffee_analysis_result* header_out,
+                           coffee_analysis_move* moves_out, coffee_analysis_root_info* root_out,
+                           float* policy_out, int* n_out) {
+  return guarded([&] {
+    need(h && h->eng && n_out, "NULL argument");
+    need(max >= 0, "max must be >= 0");
+    *n_out = h->eng->analysisDrain(max, header_out, moves_out, root_out, policy_out);
+  });
+}
+
+// The symmetry tables of a geometry without a device (coffee_root_mask / coffee_symmetry_move).
+static const DTables& hostOnlyTables(int x, int y, int w) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, int, int>, DTables*> cache;
+  std::lock_guard<std::mutex> lk(mu);
+  DTables*& t = cache[std::make_tuple(x, y, w)];
+  if(!t)
+    t = new DTables(buildTables(x, y, w));
+  return *t;
+}
+
+int coffee_root_mask(int x, int y, int win_len, const uint8_t* colours, const int32_t* hist_cell,
+                     const int32_t* hist_dir, int n_hist, const uint32_t* legal_bits, const uint32_t* avoid_bits,
+                     int mode, int prune, uint32_t* mask_out, uint32_t* syms_out) {
+  int left = 0;
+  const int rc = guarded([&] {
+    checkGeom(x, y, win_len);
+    need(colours && legal_bits && mask_out && syms_out, "NULL argument");
+    need(n_hist >= 0 && n_hist <= HIST && (n_hist == 0 || (hist_cell && hist_dir)), "n_hist must be in 0..5 with both arrays");
+    need(prune == 0 || prune == 1, "prune must be 0 or 1");
+    const DTables& T = hostOnlyTables(x, y, win_len);
+    coffee_analysis_restrict r;
+    memset(&r, 0, sizeof(r));
+    r.mode = mode;
+    if(mode != RM_NONE) {
+      need(avoid_bits != nullptr, "avoid_bits is NULL");
+      memcpy(r.avoid, avoid_bits, sizeof(r.avoid));
+    }
+    validateAnalysisRestrict(x, y, 0, r);
+    const RootGeom g{T.X, T.Y, T.A, T.P, &T.symCell[0][0], &T.symDir[0][0]};
+    RootPos p;
+    memset(&p, 0, sizeof(p));
+    for(int c = 0; c < T.A; c++) {
+      need(colours[c] <= 2, "colours must be 0, 1 or 2");
+      if(colours[c] != 0)
+        p.stones[2 * (colours[c] - 1) + (c >> 6)] |= 1ULL << (c & 63);
+    }
+    for(int k = 0; k < HIST; k++) {
+      p.histCell[k] = -1;
+      p.histDir[k] = 4;
+      if(k < n_hist && hist_cell[k] >= 0) {
+        need(hist_cell[k] < T.A && hist_dir[k] >= 0 && hist_dir[k] <= 4, "history entry out of range");
+        p.histCell[k] = hist_cell[k];
+        p.histDir[k] = hist_dir[k];
+      }
+    }
+    int masked = 0;
+    left = rmRootMask(g, p, legal_bits, r.avoid, mode, prune != 0, mask_out, syms_out, &masked);
+  });
+  return rc != COFFEE_OK ? rc : left;
+}
+
+int coffee_symmetry_move(int x, int y, int sym, int move) {
+  int image = 0;
+  const int rc = guarded([&] {
+    need(x >= 2 && y >= 2 && x <= MAX_LEN && y <= MAX_LEN, "board size must be 2..10 x 2..10");
+    need(sym >= 0 && sym < 8, "sym must be in 0..7");
+    need(move >= 0 && move < 4 * x * y, "move must be a policy position");
+    const DTables& T = hostOnlyTables(x, y, 2);
+    const RootGeom g{T.X, T.Y, T.A, T.P, &T.symCell[0][0], &T.symDir[0][0]};
+    image = rmImage(g, sym, move);
+  });
+  return rc != COFFEE_OK ? rc : image;
 }
 
 int coffee_analysis_stats_get(coffee_analysis* h, coffee_analysis_stats* out) {

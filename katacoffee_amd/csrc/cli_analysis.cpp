@@ -15,6 +15,12 @@
 // A malformed line, an unknown move string, an illegal move or an out-of-range field gets
 //   {"id":...,"error":...,"field":...}
 // and the service goes on.  End of input finishes the outstanding queries and exits 0.
+// Root restrictions (cli_analysis_query.h): the config key rootSymmetryPruning
+// (false) and the query keys includePolicy, allowMoves / avoidMoves
+// ([{"player":"B","moves":[...],"untilDepth":1}]).  rootInfo carries "symmetries", the used
+// ones; with pruning on, a pruned legal move whose orbit's survivor was searched is reported
+// as the survivor's entry with move and pv mapped and "isSymmetryOf"; "policy" (when asked)
+// has P numbers, -1 at illegal moves.
 // Without -model the stand-in network answers.  Config: the search keys of cli_config.h on
 // coffee_analysis_params_default, numAnalysisSlots (64), analysisPVLen (15),
 // nnCacheSizePowerOfTwo, nnPrecision.
@@ -31,6 +37,7 @@
 #include <vector>
 
 #include "../../include/katacoffee.h"
+#include "cli_analysis_query.h"
 #include "cli_config.h"
 #include "cli_json.h"
 #include "cli_util.h"
@@ -49,27 +56,8 @@ void must(int rc, const char* what) {
     fail(std::string(what) + ": " + coffee_last_error());
 }
 
-const char* const COORD = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ";
-
-// "ccb" -> policy position dir * A + cell, or -1.
-int parseMove(const std::string& m, int x, int y) {
-  if(m.size() != 3)
-    return -1;
-  const char* cx = strchr(COORD, m[0]);
-  const char* cy = strchr(COORD, m[1]);
-  if(!m[0] || !m[1] || !cx || !cy || cx - COORD >= x || cy - COORD >= y || m[2] < 'a' || m[2] > 'd')
-    return -1;
-  return (m[2] - 'a') * x * y + (int)(cy - COORD) * x + (int)(cx - COORD);
-}
-
-std::string moveString(int pos, int x, int y) {
-  const int A = x * y, cell = pos % A;
-  std::string s;
-  s += COORD[cell % x];
-  s += COORD[cell / x];
-  s += (char)('a' + pos / A);
-  return s;
-}
+int parseMove(const std::string& m, int x, int y) { return parseAnalysisMove(m, x, y); }
+std::string moveString(int pos, int x, int y) { return analysisMoveString(pos, x, y); }
 
 std::string num(double v) {
   char b[40];
@@ -99,12 +87,15 @@ struct Service {
   uint64_t nextId = 1;
   std::map<uint64_t, std::string> idJson;  // engine id -> the query's own id, as JSON text
   std::vector<coffee_analysis_query> waiting;  // parsed, not yet accepted by the engine
+  std::vector<coffee_analysis_restrict> waitingRestrict;  // beside them
+  std::map<uint64_t, RootQuery> rootQuery;  // engine id -> the query's root keys
+  bool prune = false;                       // rootSymmetryPruning
 
   // One input line: an error line at once, or a query queued for the engine.
   void takeLine(const std::string& line) {
     kcjson::Object o;
     std::string err;
-    if(!kcjson::parseLine(line, o, err)) {
+    if(!kcjson::parseLine(line, o, err, &analysisQuerySchema())) {
       emitError("null", "malformed query: " + err, "json");
       return;
     }
@@ -150,23 +141,58 @@ struct Service {
       }
       q.max_visits = (int32_t)v->i;
     }
+    RootQuery rq;
+    std::string field;
+    if(!parseRootKeys(o, x, y, 1 + (int)(n % 2), rq, err, field)) {
+      emitError(id, err, field);
+      return;
+    }
     q.id = nextId++;
     q.stream = (uint32_t)q.id;
     idJson[q.id] = id;
+    rootQuery[q.id] = rq;
     waiting.push_back(q);
+    waitingRestrict.push_back(rq.restrict_);
   }
 
   void submitWaiting() {
     if(waiting.empty())
       return;
     int took = 0;
-    must(coffee_analysis_submit(h, waiting.data(), (int)waiting.size(), &took), "submit");
+    must(coffee_analysis_submit2(h, waiting.data(), waitingRestrict.data(), (int)waiting.size(), &took), "submit");
     waiting.erase(waiting.begin(), waiting.begin() + took);
+    waitingRestrict.erase(waitingRestrict.begin(), waitingRestrict.begin() + took);
   }
 
-  void report(const coffee_analysis_result& r, const coffee_analysis_move* m) {
+  // One moveInfos entry: child c reported as move `move` with its PV mapped by symmetry sym
+  // (0: as searched); survivor >= 0 marks a symmetry copy.
+  std::string moveInfo(const coffee_analysis_move& c, int pla, int sym, int survivor) {
+    auto img = [&](int pos) { return sym == 0 ? pos : coffee_symmetry_move(x, y, sym, pos); };
+    const double wr = winrateFor(c.win_loss_avg, pla);
+    // lcb is the mover's utility bound in [-1, 1]; a child without a visit has none
+    const double lcb = c.visits > 0 ? 0.5 * ((double)c.lcb + 1.0) : wr;
+    std::string o = "{\"move\":\"" + moveString(img(c.move), x, y) + "\",\"visits\":" + std::to_string(c.edge_visits) +
+                    ",\"winrate\":" + num(wr) + ",\"prior\":" + num(c.prior) + ",\"lcb\":" + num(lcb) +
+                    ",\"order\":" + std::to_string(c.order) + ",\"pv\":[";
+    for(int t = 0; t < c.pv_len && t < COFFEE_ANALYSIS_MAX_PV; t++)
+      o += std::string(t ? "," : "") + "\"" + moveString(img(c.pv[t]), x, y) + "\"";
+    o += "]";
+    if(survivor >= 0)
+      o += ",\"isSymmetryOf\":\"" + moveString(survivor, x, y) + "\"";
+    return o + "}";
+  }
+
+  void report(const coffee_analysis_result& r, const coffee_analysis_move* m, const coffee_analysis_root_info& ri,
+              const float* policy) {
     const std::string id = idJson[r.id];
     idJson.erase(r.id);
+    const RootQuery rq = rootQuery[r.id];
+    rootQuery.erase(r.id);
+    if(r.status == COFFEE_ANALYSIS_NO_ALLOWED_MOVE) {
+      const char* key = rq.restrict_.mode == 2 ? "allowMoves" : "avoidMoves";
+      emitError(id, std::string(key) + " leaves no legal move", key);
+      return;
+    }
     if(r.status == COFFEE_ANALYSIS_ILLEGAL_MOVE) {
       emitError(id, "illegal move at index " + std::to_string(r.info), "moves");
       return;
@@ -181,25 +207,55 @@ struct Service {
       return;
     }
     o += ",\"rootInfo\":{\"visits\":" + std::to_string(r.visits) + ",\"winrate\":" +
-         num(winrateFor(r.win_loss_avg, r.pla)) + ",\"currentPlayer\":\"" + cur + "\"},\"moveInfos\":[";
+         num(winrateFor(r.win_loss_avg, r.pla)) + ",\"currentPlayer\":\"" + cur + "\",\"symmetries\":[";
+    bool first = true;
+    for(int sy = 0; sy < 8; sy++)
+      if((ri.symmetries >> sy) & 1u) {
+        o += std::string(first ? "" : ",") + std::to_string(sy);
+        first = false;
+      }
+    o += "]},\"moveInfos\":[";
     const int k = r.num_children;
     std::vector<int> byOrder((size_t)k, 0);
     for(int i = 0; i < k; i++)
       if(m[i].order >= 0 && m[i].order < k)
         byOrder[(size_t)m[i].order] = i;
-    for(int r2 = 0; r2 < k; r2++) {
-      const coffee_analysis_move& c = m[byOrder[(size_t)r2]];
-      const double wr = winrateFor(c.win_loss_avg, r.pla);
-      // lcb is the mover's utility bound in [-1, 1]; a child without a visit has none
-      const double lcb = c.visits > 0 ? 0.5 * ((double)c.lcb + 1.0) : wr;
-      o += std::string(r2 ? "," : "") + "{\"move\":\"" + moveString(c.move, x, y) + "\",\"visits\":" +
-           std::to_string(c.edge_visits) + ",\"winrate\":" + num(wr) + ",\"prior\":" + num(c.prior) + ",\"lcb\":" +
-           num(lcb) + ",\"order\":" + std::to_string(c.order) + ",\"pv\":[";
-      for(int t = 0; t < c.pv_len && t < COFFEE_ANALYSIS_MAX_PV; t++)
-        o += std::string(t ? "," : "") + "\"" + moveString(c.pv[t], x, y) + "\"";
-      o += "]}";
+    for(int r2 = 0; r2 < k; r2++)
+      o += std::string(r2 ? "," : "") + moveInfo(m[byOrder[(size_t)r2]], r.pla, 0, -1);
+    // symmetry pruning: every pruned legal move whose orbit's survivor was searched is the
+    // survivor's entry seen through the lowest used symmetry that takes the survivor to it
+    // (the policy marks the legal moves; avoided moves get no copies)
+    if(prune && policy && (ri.symmetries & ~1u) != 0) {
+      std::vector<int> childOf((size_t)P, -1);
+      for(int i = 0; i < k; i++)
+        if(m[i].move >= 0 && m[i].move < P)
+          childOf[(size_t)m[i].move] = i;
+      const bool have = rq.restrict_.mode != 0;
+      auto avoided = [&](int p) {
+        const bool bit = (rq.restrict_.avoid[p >> 5] >> (p & 31)) & 1u;
+        return have && (rq.restrict_.mode == 2 ? !bit : bit);
+      };
+      for(int r2 = 0; r2 < k; r2++) {
+        const coffee_analysis_move& c = m[byOrder[(size_t)r2]];
+        std::map<int, int> copies;  // pruned move -> lowest symmetry from the survivor
+        for(int sy = 7; sy >= 1; sy--)
+          if((ri.symmetries >> sy) & 1u) {
+            const int p = coffee_symmetry_move(x, y, sy, c.move);
+            if(p > c.move && p < P && policy[p] >= 0.0f && !avoided(p) && childOf[(size_t)p] < 0)
+              copies[p] = sy;
+          }
+        for(const auto& cp : copies)
+          o += "," + moveInfo(c, r.pla, cp.second, c.move);
+      }
     }
-    emit(o + "]}");
+    o += "]";
+    if(rq.includePolicy && policy) {
+      o += ",\"policy\":[";
+      for(int p = 0; p < P; p++)
+        o += std::string(p ? "," : "") + (policy[p] < 0.0f ? std::string("-1") : num(policy[p]));
+      o += "]";
+    }
+    emit(o + "}");
   }
 };
 
@@ -272,6 +328,11 @@ int analysisMain(int argc, char** argv) {
   Service sv;
   must(coffee_analysis_create(&c, &sv.h), "create analysis engine");
   must(coffee_analysis_set_uncertainty(sv.h, &s.unc), "set uncertainty");
+  // the policy travels with every result: a query's includePolicy prints it, and the symmetry
+  // copies read the legal moves off it
+  const coffee_analysis_root_options ro{s.rootSymmetryPruning, 1};
+  must(coffee_analysis_set_root_options(sv.h, &ro), "set root options");
+  sv.prune = s.rootSymmetryPruning != 0;
   sv.x = s.x;
   sv.y = s.y;
   sv.A = s.x * s.y;
@@ -281,6 +342,8 @@ int analysisMain(int argc, char** argv) {
           s.sp.max_visits, model.empty() ? "stand-in network" : model.c_str());
   std::vector<coffee_analysis_result> hdr((size_t)c.query_capacity);
   std::vector<coffee_analysis_move> mv((size_t)c.query_capacity * sv.P);
+  std::vector<coffee_analysis_root_info> rinfo((size_t)c.query_capacity);
+  std::vector<float> pol((size_t)c.query_capacity * sv.P);
   std::string buf;
   bool eof = false, skipping = false;  // skipping: inside an over-long line already reported
   char chunk[65536];
@@ -323,9 +386,9 @@ int analysisMain(int argc, char** argv) {
       continue;
     must(coffee_analysis_step(sv.h, 16, nullptr), "step");
     int n = 0;
-    must(coffee_analysis_drain(sv.h, c.query_capacity, hdr.data(), mv.data(), &n), "drain");
+    must(coffee_analysis_drain2(sv.h, c.query_capacity, hdr.data(), mv.data(), rinfo.data(), pol.data(), &n), "drain");
     for(int i = 0; i < n; i++)
-      sv.report(hdr[(size_t)i], mv.data() + (size_t)i * sv.P);
+      sv.report(hdr[(size_t)i], mv.data() + (size_t)i * sv.P, rinfo[(size_t)i], pol.data() + (size_t)i * sv.P);
   }
   coffee_analysis_stats st;
   must(coffee_analysis_stats_get(sv.h, &st), "stats");

@@ -61,6 +61,9 @@ struct Settings {
   // off) by the command before applyConfig; off unless the config turns it on, for all three
   // commands (the reference's loader defaults it on for analysis, GTP and match, setup.cpp:539-562)
   coffee_uncertainty_params unc;
+  // rootSymmetryPruning (`katago analysis` only): off unless the config turns it on -- the
+  // reference's loader defaults it on for analysis and GTP (setup.cpp:639-644)
+  int32_t rootSymmetryPruning = 0;
   StartPosSettings startPos;  // off unless startPosesProb > 0 and a source is named
 };
 
@@ -245,6 +248,7 @@ inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& 
       throw std::invalid_argument("nnPrecision must be auto, corrected, accurate, fast or fastLayered");
   }
   applySearchConfig(r, s.sp, s.unc);
+  r.getb("rootSymmetryPruning", s.rootSymmetryPruning);
   // start positions (play.cpp:186-196 getters: the same ranges)
   r.gets("startPosesFromSgfDir", s.startPos.sgfDirs);
   r.gets("startPosesFile", s.startPos.file);

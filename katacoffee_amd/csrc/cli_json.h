@@ -1,8 +1,11 @@
 // The JSON reader of `katago analysis` (cli_analysis.cpp): exactly what its query lines need
 // -- one flat object per line whose values are strings, integers or arrays of strings -- and
 // nothing else.  Anything outside that (nesting, numbers with a fraction, literals, bad UTF-8,
-// control characters, over-long input) is rejected with a message; nothing recurses, so no
-// input can exhaust the stack.  Host-only and header-only; compiles on its own.
+// control characters, over-long input) is rejected with a message.  A caller's Schema may name
+// keys that also take a true / false literal or an array of flat objects (the allowMoves /
+// avoidMoves shape); the objects inside such an array take the flat values only, so the depth
+// is two at most and no input can exhaust the stack.  Host-only and header-only; compiles on
+// its own.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -16,11 +19,27 @@ constexpr size_t MAX_FIELDS = 64;      // keys of the object
 constexpr size_t MAX_ITEMS = 1024;     // elements of one array
 constexpr size_t MAX_STRING = 4096;    // bytes of one string
 
+struct Object;
 struct Value {
-  enum Kind { STRING, INT, STRINGS } kind = STRING;
+  // BOOL and OBJECTS only under the keys a Schema names (parseLine)
+  enum Kind { STRING, INT, STRINGS, BOOL, OBJECTS } kind = STRING;
   std::string s;
-  long long i = 0;
+  long long i = 0;  // BOOL: 0 / 1
   std::vector<std::string> a;
+  std::vector<Object> objs;  // OBJECTS: flat objects (strings, integers, arrays of strings)
+};
+
+// The keys of the top-level object that take more than the flat values: a true / false literal
+// (includePolicy) or an array of flat objects (allowMoves, avoidMoves).  Null-terminated lists.
+struct Schema {
+  const char* const* boolKeys = nullptr;
+  const char* const* objectArrayKeys = nullptr;
+  static bool has(const char* const* keys, const std::string& k) {
+    for(; keys && *keys; keys++)
+      if(k == *keys)
+        return true;
+    return false;
+  }
 };
 
 struct Object {
@@ -222,11 +241,46 @@ inline bool parseInt(Cursor& c, long long& out) {
   return true;
 }
 
-inline bool parseValue(Cursor& c, Value& v) {
+inline bool parseFields(Cursor& c, Object& out, const Schema* schema);
+
+// key / schema: the value's key in the top-level object (schema null: inside an array's
+// object, where only the flat values are taken -- the depth is bounded by that).
+inline bool parseValue(Cursor& c, Value& v, const Schema* schema = nullptr, const std::string& key = std::string()) {
   c.ws();
   if(c.p >= c.s.size())
     return c.fail("truncated line");
   const char ch = c.s[c.p];
+  if(schema && Schema::has(schema->boolKeys, key) && (ch == 't' || ch == 'f')) {
+    const char* word = ch == 't' ? "true" : "false";
+    const size_t n = ch == 't' ? 4 : 5;
+    if(c.s.compare(c.p, n, word) != 0)
+      return c.fail("expected true or false");
+    c.p += n;
+    v.kind = Value::BOOL;
+    v.i = ch == 't' ? 1 : 0;
+    return true;
+  }
+  if(schema && Schema::has(schema->objectArrayKeys, key) && ch == '[') {
+    c.p++;
+    v.kind = Value::OBJECTS;
+    v.objs.clear();
+    if(c.eat(']'))
+      return true;
+    for(;;) {
+      if(v.objs.size() >= MAX_ITEMS)
+        return c.fail("array too long");
+      if(!c.eat('{'))
+        return c.fail(c.p >= c.s.size() ? "truncated line" : "expected an object");
+      v.objs.emplace_back();
+      if(!parseFields(c, v.objs.back(), nullptr))
+        return false;
+      if(c.eat(','))
+        continue;
+      if(c.eat(']'))
+        return true;
+      return c.fail(c.p >= c.s.size() ? "truncated line" : "expected ',' or ']'");
+    }
+  }
   if(ch == '"') {
     v.kind = Value::STRING;
     return parseString(c, v.s);
@@ -262,10 +316,37 @@ inline bool parseValue(Cursor& c, Value& v) {
   }
 }
 
+// An object's fields up to and including its '}' (the '{' is consumed).
+inline bool parseFields(Cursor& c, Object& out, const Schema* schema) {
+  if(c.eat('}'))
+    return true;
+  for(;;) {
+    if(out.fields.size() >= MAX_FIELDS)
+      return c.fail("too many keys");
+    std::string key;
+    if(!parseString(c, key))
+      return false;
+    if(out.find(key))
+      return c.fail("duplicate key '" + key + "'");
+    if(!c.eat(':'))
+      return c.fail(c.p >= c.s.size() ? "truncated line" : "expected ':'");
+    Value v;
+    if(!parseValue(c, v, schema, key))
+      return false;
+    out.fields.emplace_back(std::move(key), std::move(v));
+    if(c.eat(','))
+      continue;
+    if(c.eat('}'))
+      return true;
+    return c.fail(c.p >= c.s.size() ? "truncated line" : "expected ',' or '}'");
+  }
+}
+
 }  // namespace detail
 
-// Parses one line into out; on failure returns false with a message in err.
-inline bool parseLine(const std::string& line, Object& out, std::string& err) {
+// Parses one line into out; on failure returns false with a message in err.  schema (null:
+// flat values only): the keys that take a literal or an array of flat objects.
+inline bool parseLine(const std::string& line, Object& out, std::string& err, const Schema* schema = nullptr) {
   out.fields.clear();
   if(line.size() > MAX_LINE) {
     err = "line longer than " + std::to_string(MAX_LINE) + " bytes";
@@ -280,35 +361,8 @@ inline bool parseLine(const std::string& line, Object& out, std::string& err) {
     c.fail(c.p >= line.size() ? "empty line" : "expected '{'");
     return bad();
   }
-  if(!c.eat('}')) {
-    for(;;) {
-      if(out.fields.size() >= MAX_FIELDS) {
-        c.fail("too many keys");
-        return bad();
-      }
-      std::string key;
-      if(!detail::parseString(c, key))
-        return bad();
-      if(out.find(key)) {
-        c.fail("duplicate key '" + key + "'");
-        return bad();
-      }
-      if(!c.eat(':')) {
-        c.fail(c.p >= line.size() ? "truncated line" : "expected ':'");
-        return bad();
-      }
-      Value v;
-      if(!detail::parseValue(c, v))
-        return bad();
-      out.fields.emplace_back(std::move(key), std::move(v));
-      if(c.eat(','))
-        continue;
-      if(c.eat('}'))
-        break;
-      c.fail(c.p >= line.size() ? "truncated line" : "expected ',' or '}'");
-      return bad();
-    }
-  }
+  if(!detail::parseFields(c, out, schema))
+    return bad();
   c.ws();
   if(c.p != line.size()) {
     c.fail("text after the object");

@@ -23,6 +23,7 @@
 #pragma once
 #include "../../include/katacoffee.h"
 #include "kc_common.h"
+#include "rootmask.h"
 #include "startpos.h"
 #include "uncertainty.h"
 
@@ -207,10 +208,15 @@ struct FinRec {
 };
 
 // Analysis: the query a slot holds (busy 0: the slot is idle).
+// syms / numMasked: the query's used root symmetries and masked legal root moves (rootmask.h).
 struct AnalysisSlot {
   uint64_t id;
-  int32_t busy, pad;
+  int32_t busy;
+  uint32_t syms;
+  int32_t numMasked, pad;
 };
+static_assert(RM_AREA == MAX_AREA && RM_WORDS == (MAX_P + 31) / 32, "rootmask.h geometry");
+static_assert(sizeof(coffee_analysis_restrict) == 4 * (RM_QUERY_WORDS + 1), "coffee_analysis_restrict layout");
 // SearchDev::aCtr entries: queries popped from the ring, queries submitted (written by the host
 // on the engine stream, between kernels), results written, and the stats' loaded / finished /
 // rejected counts.
@@ -397,6 +403,13 @@ struct SearchDev {
   int32_t matchPerSide, matchSharedNet;
   SP sp1;
   Unc unc1;
+  // root move restrictions of analysis (rootmask.h).  rootMask is null on every
+  // other engine: rareLeaf then leaves the root's noised policy as it is.
+  DPtr<uint32_t> rootMask;                       // [G][ceil(P/32)] the slot's masked root moves
+  DPtr<const coffee_analysis_restrict> aRestrict;  // [aCap] beside aQuery
+  DPtr<coffee_analysis_root_info> aRootInfo;     // [aCap] beside aRes
+  DPtr<float> aPolicy;                           // [aCap][P] beside aRes (null: no policy output)
+  int32_t aPrune, aPad;
 };
 
 // Match play: the candidate (net 1) plays black (player 1) in game number n of global

@@ -1815,6 +1815,17 @@ __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, in
       DRng rng{s.rngSeed, s.rngCtr};
       noiseAndTemp(v, s, rng, rp, v.rootNoised(), scratch);
       s.rngCtr = rng.ctr;
+      // analysis: the query's masked root moves (analysisRefill) leave the noised policy, after
+      // noise and temperature were drawn over every legal move -- the root selection skips
+      // entries below 0 among its children and in its scan for the next one
+      if(d.rootMask.p != nullptr) {
+        const uint32_t* mk = d.rootMask + (size_t)g * ((P + 31) >> 5);
+        float* rn = v.rootNoised();
+        waveSync();
+        for(int p = v.lane; p < P; p += 64)
+          if((mk[p >> 5] >> (p & 31)) & 1u)
+            rn[p] = -1.0f;
+      }
       s.phase = PH_SEARCH;
       needCommit = v.nodes()[s.rootIdx].visits >= (uint32_t)s.visitLimit;
     }
@@ -4250,6 +4261,83 @@ KC_D int newResult(const SearchDev& d, int lane) {
   return bcastLane(r, 0);
 }
 
+// The bits 1..7 any lane has set (uniform).
+KC_D uint32_t waveOrSyms(uint32_t x) {
+  uint32_t r = 0;
+#pragma unroll
+  for(int s = 1; s < 8; s++)
+    r |= ballot((x >> s) & 1u) != 0 ? 1u << s : 0u;
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)r);
+}
+
+// The mask of the replayed position s.root under ring entry qi's restriction (rootmask.h, the
+// rule coffee_root_mask runs on the host): the words into the slot's rootMask row, the used
+// symmetries and the number of masked legal moves into syms / masked.  Returns the number of
+// legal moves left unmasked.  Lane l takes the cells and positions l, l + 64, ...; every
+// result is uniform.  Out of line like rareLeaf (arguments by value, the game's LDS copy
+// through a pointer between fences).
+// Returns the used symmetries (bits 0-7), the masked legal moves (bits 8-16) and the legal
+// moves left unmasked (bits 17-25).
+template <bool W1>
+__device__ __noinline__ uint32_t rootMaskWave(const SearchDev* dp, const DTables* Tp, int g, const GameDev* gs, int qi) {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  const SearchDev& d = *uniformConst(dp);
+  const DTables& T = *uniformConst(Tp);
+  const GameDev& s = *uniformPtr(gs);
+  g = __builtin_amdgcn_readfirstlane(g);
+  qi = __builtin_amdgcn_readfirstlane(qi);
+  GV v(d, T, g);
+  const int A = d.A, P = d.P, W = (P + 31) >> 5;
+  __shared__ uint32_t avoidW[RM_WORDS];
+  const RootGeom rg{T.X, T.Y, A, P, &T.symCell[0][0], &T.symDir[0][0]};
+  RootPos rp;
+  rp.stones[0] = s.root.stones[0].lo;
+  rp.stones[1] = s.root.stones[0].hi;
+  rp.stones[2] = s.root.stones[1].lo;
+  rp.stones[3] = s.root.stones[1].hi;
+#pragma unroll
+  for(int k = 0; k < 5; k++) {
+    rp.histCell[k] = hCell(s.root, k);
+    rp.histDir[k] = hDir(s.root, k);
+  }
+  uint32_t used = rmGeomSyms(rg);
+  used &= ~rmHistoryBroken(rg, rp, used);
+  used = (uint32_t)__builtin_amdgcn_readfirstlane((int)used);
+  used &= ~waveOrSyms(rmStonesBroken(rg, rp, used, v.lane, 64));
+  const coffee_analysis_restrict* rq = d.aRestrict + qi;
+  const int mode = __builtin_amdgcn_readfirstlane((int)rq->mode);
+  const bool have = mode == RM_AVOID || mode == RM_ALLOW;
+  if(have) {
+    // (every lane writes the same words)
+    uint32_t qw[RM_QUERY_WORDS];
+#pragma unroll
+    for(int w = 0; w < RM_QUERY_WORDS; w++)
+      qw[w] = rq->avoid[w];
+    rmAvoidWords(P, qw, mode, avoidW);
+    waveSync();
+    used &= ~waveOrSyms(rmAvoidBroken(rg, avoidW, used, v.lane, 64));
+  }
+  uint32_t* mk = d.rootMask + (size_t)v.g * W;
+  const bool prune = d.aPrune != 0;
+  int left = 0, masked = 0;
+  for(int base = 0; base < P; base += 64) {
+    const int p = base + v.lane;
+    const bool legal = p < P && isLegal<W1>(T, s.root, p % A, p / A);
+    const bool m = p < P && rmMasked(rg, have ? avoidW : nullptr, used, prune, p, legal);
+    const uint64_t bm = ballot(m), bl = ballot(legal);
+    masked += __popcll(bm & bl);
+    left += __popcll(bl & ~bm);
+    if(v.lane == 0) {
+      mk[base >> 5] = (uint32_t)bm;
+      if((base >> 5) + 1 < W)
+        mk[(base >> 5) + 1] = (uint32_t)(bm >> 32);
+    }
+  }
+  waveSync();
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  return used | ((uint32_t)masked << 8) | ((uint32_t)left << 17);
+}
+
 // Gives the slot the next queued query, or leaves it idle.  A query's moves are replayed from
 // the empty board with the device rules, each checked before it is played; an illegal move, a
 // move list that ends the game and a position without a legal move are answered at once (no
@@ -4257,18 +4345,32 @@ KC_D int newResult(const SearchDev& d, int lane) {
 // fresh search the way startForkGame starts a forked game: stream seeded by startGame's
 // formula from (seed, stream, game_num), game hashes from its first two draws, cleared tables,
 // the replayed moves as unsearched turn records.  s: the slot's LDS copy (stored by the caller).
+//
+// One query per call of analysisRefillOne, which runs out of line like rareLeaf (arguments by
+// value, the game's LDS copy through a pointer between fences) and returns REFILL_IDLE (nothing
+// queued: the slot is idle), REFILL_LOADED or REFILL_ANSWERED (answered without a search: the
+// caller tries the next query).  Every query's replay thus starts from the function's entry,
+// with every lane active for its wave-wide rules, whatever path answered the query before it.
+enum { REFILL_IDLE = 0, REFILL_LOADED = 1, REFILL_ANSWERED = 2 };
 template <bool W1>
-KC_D void analysisRefill(const GV& v, GameDev& s) {
-  const SearchDev& d = v.d;
+__device__ __noinline__ int analysisRefillOne(const SearchDev* dp, const DTables* Tp, int g, GameDev* gs) {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  const SearchDev& d = *uniformConst(dp);
+  GameDev& s = *uniformPtr(gs);
+  g = __builtin_amdgcn_readfirstlane(g);
+  GV v(d, *uniformConst(Tp), g);
+  bindGame<false>(v, s);
   const int A = d.A, P = d.P;
-  for(;;) {
+  {
     const int qi = popQuery(d, v.lane);
     if(qi < 0) {
       s.phase = PH_COMMIT;
       s.leafKind = LEAF_NONE;
       if(v.lane == 0)
         d.aSlot[v.g].busy = 0;
-      return;
+      waveSync();
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      return REFILL_IDLE;
     }
     const coffee_analysis_query* q = d.aQuery + qi;
     const uint64_t id = q->id;
@@ -4311,11 +4413,38 @@ KC_D void analysisRefill(const GV& v, GameDev& s) {
         r.turn = s.root.turn;
         r.pla = s.root.pla;
         d.aRes[ri] = r;
+        d.aRootInfo[ri] = coffee_analysis_root_info{0u, 0};
         atomicAdd(&d.aCtr[AC_LOADED], 1ull);
         atomicAdd(&d.aCtr[AC_FINISHED], 1ull);
         atomicAdd(&d.aCtr[AC_REJECTED], 1ull);
       }
-      continue;
+      waveSync();
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      return REFILL_ANSWERED;
+    }
+    // the root restrictions, once per query; a mask that leaves no legal move is answered at
+    // once like the cases above (symmetry pruning alone always leaves each orbit's survivor)
+    const uint32_t rm = (uint32_t)__builtin_amdgcn_readfirstlane((int)rootMaskWave<W1>(&d, &v.T, v.g, &s, qi));
+    const uint32_t syms = rm & 0xFFu;
+    const int masked = (int)((rm >> 8) & 0x1FFu), left = (int)(rm >> 17);
+    if(left == 0) {
+      const int ri = newResult(d, v.lane);
+      if(v.lane == 0) {
+        coffee_analysis_result r;
+        memset(&r, 0, sizeof(r));
+        r.id = id;
+        r.status = COFFEE_ANALYSIS_NO_ALLOWED_MOVE;
+        r.turn = s.root.turn;
+        r.pla = s.root.pla;
+        d.aRes[ri] = r;
+        d.aRootInfo[ri] = coffee_analysis_root_info{syms, masked};
+        atomicAdd(&d.aCtr[AC_LOADED], 1ull);
+        atomicAdd(&d.aCtr[AC_FINISHED], 1ull);
+        atomicAdd(&d.aCtr[AC_REJECTED], 1ull);
+      }
+      waveSync();
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      return REFILL_ANSWERED;
     }
     s.rngSeed = mix64(d.seed ^ mix64(((uint64_t)q->stream << 32) | (uint32_t)q->game_num));
     s.gameNum = (int32_t)q->game_num;
@@ -4355,11 +4484,20 @@ KC_D void analysisRefill(const GV& v, GameDev& s) {
     if(v.lane == 0) {
       d.aSlot[v.g].id = id;
       d.aSlot[v.g].busy = 1;
+      d.aSlot[v.g].syms = syms;
+      d.aSlot[v.g].numMasked = masked;
       atomicAdd(&d.aCtr[AC_LOADED], 1ull);
     }
     waveSync();
-    return;
   }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  return REFILL_LOADED;
+}
+template <bool W1>
+KC_D void analysisRefill(const GV& v, GameDev& s) {
+  while(__builtin_amdgcn_readfirstlane(analysisRefillOne<W1>(&v.d, &v.T, v.g, &s)) == REFILL_ANSWERED) {
+  }
+  waveSync();
 }
 
 // Every slot idle (after kInit started a game in each).
@@ -4505,7 +4643,13 @@ __global__ void __launch_bounds__(64) kAnalysisReport(const SearchDev* __restric
     r.num_children = k;
     r.pad = 0;
     d.aRes[ri] = r;
+    d.aRootInfo[ri] = coffee_analysis_root_info{d.aSlot[g].syms, d.aSlot[g].numMasked};
     atomicAdd(&d.aCtr[AC_FINISHED], 1ull);
+  }
+  if(d.aPolicy.p != nullptr) {  // the root's network policy as stored (no temperature, noise or mask)
+    float* po = d.aPolicy + (size_t)ri * d.P;
+    for(int p = v.lane; p < d.P; p += 64)
+      po[p] = rp[p];
   }
   waveSync();
   analysisRefill<W1_OF<NI>>(v, s);

@@ -302,6 +302,10 @@ SelfplayEngine::SelfplayEngine(const coffee_analysis_config& c) : SelfplayEngine
   d.aMoves = devAlloc<coffee_analysis_move>(owned_, (size_t)d.aCap * d.P);
   d.aCtr = devAlloc<unsigned long long>(owned_, AC_N);
   d.aSlot = devAlloc<AnalysisSlot>(owned_, (size_t)d.G);
+  // root restrictions (rootmask.h): a zeroed ring entry is "no restriction"
+  d.rootMask = devAlloc<uint32_t>(owned_, (size_t)d.G * ((d.P + 31) / 32));
+  d.aRestrict = devAlloc<coffee_analysis_restrict>(owned_, (size_t)d.aCap);
+  d.aRootInfo = devAlloc<coffee_analysis_root_info>(owned_, (size_t)d.aCap);
   KC_HIP(hipMemcpy(dd_, &d, sizeof(SearchDev), hipMemcpyHostToDevice));
   launchSelfplayInit(d, dd_, stream_);  // again, now in analysis mode: every slot idle
   KC_HIP(hipStreamSynchronize(stream_));
@@ -677,6 +681,41 @@ void SelfplayEngine::setUncertainty(const coffee_uncertainty_params& p) {
   KC_HIP(hipMemcpy(&dd_->unc, &hd_.unc, sizeof(Unc), hipMemcpyHostToDevice));
 }
 
+void SelfplayEngine::setRootOptions(const coffee_analysis_root_options& o) {
+  if(!hd_.analysisMode)
+    throw std::invalid_argument("not an analysis engine");
+  if((o.root_symmetry_pruning != 0 && o.root_symmetry_pruning != 1) || (o.include_policy != 0 && o.include_policy != 1))
+    throw std::invalid_argument("set_root_options: root_symmetry_pruning and include_policy must be 0 or 1");
+  // a query's mask is computed when a slot loads it: only before the first query
+  if(aSubmitted_ > 0)
+    throw std::invalid_argument("set_root_options: only before the first query");
+  hd_.aPrune = o.root_symmetry_pruning;
+  if(o.include_policy && hd_.aPolicy.p == nullptr)
+    hd_.aPolicy = devAlloc<float>(owned_, (size_t)hd_.aCap * hd_.P);
+  aIncludePolicy_ = o.include_policy != 0;
+  // nothing runs yet (the constructor synchronised its initialisation): a plain copy.  A policy
+  // ring allocated by an earlier call stays allocated; the kernels see it only while asked for
+  SearchDev dev = hd_;
+  if(!aIncludePolicy_)
+    dev.aPolicy = nullptr;
+  KC_HIP(hipMemcpy(&dd_->aPrune, &dev.aPrune, sizeof(int32_t), hipMemcpyHostToDevice));
+  KC_HIP(hipMemcpy(&dd_->aPolicy, &dev.aPolicy, sizeof(dev.aPolicy), hipMemcpyHostToDevice));
+}
+
+void validateAnalysisRestrict(int x, int y, uint64_t id, const coffee_analysis_restrict& r) {
+  const int P = 4 * x * y;
+  const std::string who = "analysis query " + std::to_string(id);
+  if(r.mode < RM_NONE || r.mode > RM_ALLOW)
+    throw std::invalid_argument(who + ": restrict mode must be 0 (none), 1 (avoid) or 2 (allow)");
+  if(r.mode == RM_NONE)
+    return;
+  if(P > 32 * RM_QUERY_WORDS)
+    throw std::invalid_argument(who + ": avoid / allow sets need a board of at most " +
+                                std::to_string(32 * RM_QUERY_WORDS) + " positions");
+  if(rmBitsPastP(P, r.avoid))
+    throw std::invalid_argument(who + ": avoid / allow bit at a position >= " + std::to_string(P));
+}
+
 // ---- start positions (startpos.h) ----
 
 void validateStartPosParams(const coffee_start_positions_params& p) {
@@ -947,7 +986,7 @@ void SelfplayEngine::matchStats(coffee_match_stats& out) {
   }
 }
 
-int SelfplayEngine::analysisSubmit(const coffee_analysis_query* q, int n) {
+int SelfplayEngine::analysisSubmit(const coffee_analysis_query* q, const coffee_analysis_restrict* rs, int n) {
   if(!hd_.analysisMode)
     throw std::invalid_argument("not an analysis engine");
   for(int i = 0; i < n; i++) {
@@ -955,6 +994,8 @@ int SelfplayEngine::analysisSubmit(const coffee_analysis_query* q, int n) {
     if(q[i].max_visits > hd_.cap - 4)
       throw std::invalid_argument("analysis query " + std::to_string(q[i].id) + ": max_visits must be <= node_cap - 4 (" +
                                   std::to_string(hd_.cap - 4) + ")");
+    if(rs)
+      validateAnalysisRestrict(xLen_, yLen_, q[i].id, rs[i]);
   }
   const uint64_t cap = (uint64_t)hd_.aCap;
   const int take = (int)std::min<uint64_t>((uint64_t)std::max(n, 0), cap - (aSubmitted_ - aDrained_));
@@ -969,13 +1010,28 @@ int SelfplayEngine::analysisSubmit(const coffee_analysis_query* q, int n) {
   if((uint64_t)take > run0)
     KC_HIP(hipMemcpy(hd_.aQuery, q + run0, sizeof(coffee_analysis_query) * ((uint64_t)take - run0),
                      hipMemcpyHostToDevice));
+  // the restrictions beside them (none given: zeroed entries, mode 0)
+  std::vector<coffee_analysis_restrict> none;
+  if(!rs && take > 0) {
+    none.assign((size_t)take, coffee_analysis_restrict{});
+    rs = none.data();
+  }
+  coffee_analysis_restrict* ring = const_cast<coffee_analysis_restrict*>(hd_.aRestrict.p);
+  if(run0 > 0)
+    KC_HIP(hipMemcpy(ring + first, rs, sizeof(coffee_analysis_restrict) * run0, hipMemcpyHostToDevice));
+  if((uint64_t)take > run0)
+    KC_HIP(hipMemcpy(ring, rs + run0, sizeof(coffee_analysis_restrict) * ((uint64_t)take - run0),
+                     hipMemcpyHostToDevice));
   aSubmitted_ += (uint64_t)take;
   return take;
 }
 
-int SelfplayEngine::analysisDrain(int max, coffee_analysis_result* header, coffee_analysis_move* moves) {
+int SelfplayEngine::analysisDrain(int max, coffee_analysis_result* header, coffee_analysis_move* moves,
+                                  coffee_analysis_root_info* rootInfo, float* policy) {
   if(!hd_.analysisMode)
     throw std::invalid_argument("not an analysis engine");
+  if(policy && !aIncludePolicy_)
+    throw std::invalid_argument("policy_out: the engine was not set to include_policy (coffee_analysis_set_root_options)");
   sync();
   unsigned long long written = 0;
   KC_HIP(hipMemcpy(&written, hd_.aCtr + AC_RESULTS, 8, hipMemcpyDeviceToHost));
@@ -989,11 +1045,19 @@ int SelfplayEngine::analysisDrain(int max, coffee_analysis_result* header, coffe
     KC_HIP(hipMemcpy(header, hd_.aRes + first, sizeof(coffee_analysis_result) * run0, hipMemcpyDeviceToHost));
     if(moves)
       KC_HIP(hipMemcpy(moves, hd_.aMoves + first * P, sizeof(coffee_analysis_move) * P * run0, hipMemcpyDeviceToHost));
+    if(rootInfo)
+      KC_HIP(hipMemcpy(rootInfo, hd_.aRootInfo + first, sizeof(coffee_analysis_root_info) * run0, hipMemcpyDeviceToHost));
+    if(policy)
+      KC_HIP(hipMemcpy(policy, hd_.aPolicy + first * P, sizeof(float) * P * run0, hipMemcpyDeviceToHost));
   }
   if(run1 > 0) {
     KC_HIP(hipMemcpy(header + run0, hd_.aRes, sizeof(coffee_analysis_result) * run1, hipMemcpyDeviceToHost));
     if(moves)
       KC_HIP(hipMemcpy(moves + run0 * P, hd_.aMoves, sizeof(coffee_analysis_move) * P * run1, hipMemcpyDeviceToHost));
+    if(rootInfo)
+      KC_HIP(hipMemcpy(rootInfo + run0, hd_.aRootInfo, sizeof(coffee_analysis_root_info) * run1, hipMemcpyDeviceToHost));
+    if(policy)
+      KC_HIP(hipMemcpy(policy + run0 * P, hd_.aPolicy, sizeof(float) * P * run1, hipMemcpyDeviceToHost));
   }
   // a ring entry's records past its children belong to earlier results
   if(moves)
@@ -1001,6 +1065,11 @@ int SelfplayEngine::analysisDrain(int max, coffee_analysis_result* header, coffe
       const uint64_t k = (uint64_t)std::min<int64_t>(std::max<int64_t>(header[i].num_children, 0), (int64_t)P);
       memset(moves + (uint64_t)i * P + k, 0, sizeof(coffee_analysis_move) * (P - k));
     }
+  // ... and so does the policy row of a result without a search
+  if(policy)
+    for(int i = 0; i < n; i++)
+      if(header[i].status != COFFEE_ANALYSIS_OK)
+        memset(policy + (uint64_t)i * P, 0, sizeof(float) * P);
   aDrained_ += (uint64_t)n;
   return n;
 }

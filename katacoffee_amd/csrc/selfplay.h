@@ -39,6 +39,9 @@ void validateAnalysisConfig(const coffee_analysis_config& c);
 // A query's host-side checks at board x * y (throws std::invalid_argument naming the field):
 // num_moves in 0..x*y, every move < 4*x*y, max_visits >= 0.
 void validateAnalysisQuery(int x, int y, const coffee_analysis_query& q);
+// A query's root restriction at board x * y: mode 0..2, no bit at a position >= 4*x*y, a set
+// only where the board's positions fit its words.
+void validateAnalysisRestrict(int x, int y, uint64_t id, const coffee_analysis_restrict& r);
 
 class SelfplayEngine {
  public:
@@ -65,8 +68,13 @@ class SelfplayEngine {
   void matchStats(coffee_match_stats& out);
   // Analysis mode: queries into the device ring on the engine stream (returns how many fit),
   // finished results out of it (returns their number), the counters.
-  int analysisSubmit(const coffee_analysis_query* q, int n);
-  int analysisDrain(int max, coffee_analysis_result* header, coffee_analysis_move* moves);
+  // rs (nullptr: none): the queries' root restrictions; rootInfo / policy (nullptr: skipped): the
+  // results' used symmetries and masked-move counts, and with include_policy the root policies
+  int analysisSubmit(const coffee_analysis_query* q, const coffee_analysis_restrict* rs, int n);
+  int analysisDrain(int max, coffee_analysis_result* header, coffee_analysis_move* moves,
+                    coffee_analysis_root_info* rootInfo = nullptr, float* policy = nullptr);
+  // Root restrictions: only before the first submitted query.
+  void setRootOptions(const coffee_analysis_root_options& o);
   void analysisStats(coffee_analysis_stats& out);
   int drain(int maxRows, uint8_t* bin, float* glob, int16_t* pol, float* gt, int8_t* val, int32_t* meta);
   // header [g][4]; match mode [g][5], the candidate's colour last
@@ -112,6 +120,7 @@ class SelfplayEngine {
   static coffee_selfplay_config analysisBase(const coffee_analysis_config& c);
   // analysis: queries submitted / results drained so far
   uint64_t aSubmitted_ = 0, aDrained_ = 0;
+  bool aIncludePolicy_ = false;
   const DTables* T_ = nullptr;
   // Per-network state: self-play holds one network, match play two (each resolves its
   // precision and runs its audit on its own batches).

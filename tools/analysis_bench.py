@@ -3,6 +3,7 @@
 
   python tools/analysis_bench.py [--arch b6c96] [--slots 4096] [--visits 500] [--rounds 2000]
                                  [--warmup 1000] [--precision default] [--repeats 3]
+                                 [--root-symmetry-pruning]
 
 A kc.Analysis engine is kept fed with queries (random legal openings of 0..8 moves, made with
 the device rules) so that its ring never runs dry; a kc.Selfplay engine with the same net,
@@ -11,7 +12,11 @@ comparison.  Each figure is taken over `repeats` timed windows of `rounds` round
 `warmup` rounds, host clock around work that ends in a device synchronise; submissions and
 drains happen between the windows' steps and are part of the analysis time, as they are for a
 service.  Prints one JSON line.  The round kernels are the same in both engines, so the
-playouts per second should agree; a gap means idle slots or a refill stall."""
+playouts per second should agree; a gap means idle slots or a refill stall.
+--root-symmetry-pruning turns the analysis engine's root symmetry pruning on (DESIGN.md 8f);
+with or without it the line also carries the drained results' mean root children and mean
+principal-variation length and, where the library reports them, the share of results whose
+used symmetry group was not trivial."""
 import argparse
 import json
 import os
@@ -64,6 +69,8 @@ def main():
     ap.add_argument("--cache-log2", type=int, default=21)
     ap.add_argument("--uncertainty", action="store_true",
                     help="uncertainty weighting on (set_uncertainty(use_uncertainty=1), default values) in both engines")
+    ap.add_argument("--root-symmetry-pruning", action="store_true",
+                    help="root symmetry pruning on in the analysis engine")
     a = ap.parse_args()
     search = kc.default_analysis_params(max_visits=a.visits)
     pool = openings(8192, 8, 5)
@@ -74,7 +81,11 @@ def main():
         an = kc.Analysis(X, Y, W, num_slots=a.slots, model_path=path, search=search, query_capacity=4 * a.slots,
                          **common)
         an.set_uncertainty(use_uncertainty=int(a.uncertainty))
+        has_root = hasattr(kc.lib(), "coffee_root_mask")  # (absent in earlier builds run as A/B references)
+        if a.root_symmetry_pruning:
+            an.set_root_options(root_symmetry_pruning=True)
         next_id = [0]
+        tally = {"results": 0, "children": 0, "pv": 0, "pv_n": 0, "nontrivial": 0}
 
         def feed():
             free = an.query_capacity - (next_id[0] - feed.drained)
@@ -90,10 +101,22 @@ def main():
                 n = min(a.step, rounds - done)
                 an.step(n)
                 done += n
-                feed.drained += len(an.drain()[0])
+                res = an.drain(with_root=True) if has_root else an.drain()
+                h, m = res[0], res[1]
+                feed.drained += len(h)
+                ok = h["status"] == 0
+                tally["results"] += int(ok.sum())
+                tally["children"] += int(h["num_children"][ok].sum())
+                valid = np.arange(m.shape[1])[None, :] < h["num_children"][:, None]
+                tally["pv"] += int(m["pv_len"][valid].sum())
+                tally["pv_n"] += int(valid.sum())
+                if has_root:
+                    tally["nontrivial"] += int((res[2]["symmetries"][ok] != 1).sum())
 
         run(a.warmup)
         an.sync()
+        for k in tally:
+            tally[k] = 0
         s0, secs = an.stats(), []
         for _ in range(a.repeats):
             t0 = time.perf_counter()
@@ -129,7 +152,12 @@ def main():
                      "playouts_per_s": round((s1["playouts"] - s0["playouts"]) / t_an, 0),
                      "us_per_round": round(1e6 * t_an / (a.rounds * a.repeats), 2),
                      "window_s": [round(x, 4) for x in secs],
-                     "nn_precision": kc.PRECISION_NAMES.get(s1["nn_precision"], "stand-in")},
+                     "nn_precision": kc.PRECISION_NAMES.get(s1["nn_precision"], "stand-in"),
+                     "root_symmetry_pruning": bool(a.root_symmetry_pruning),
+                     "mean_root_children": round(tally["children"] / max(tally["results"], 1), 2),
+                     "mean_pv_len": round(tally["pv"] / max(tally["pv_n"], 1), 3),
+                     "nontrivial_group_share": round(tally["nontrivial"] / max(tally["results"], 1), 4) if has_root
+                     else None},
         "selfplay": {"playouts_per_s": round((p1["playouts"] - p0["playouts"]) / t_sp, 0),
                      "us_per_round": round(1e6 * t_sp / (a.rounds * a.repeats), 2),
                      "window_s": [round(x, 4) for x in ssecs]},
