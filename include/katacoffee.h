@@ -631,6 +631,61 @@ int coffee_selfplay_set_uncertainty(coffee_selfplay* h, const coffee_uncertainty
 int coffee_match_set_uncertainty(coffee_match* h, const coffee_uncertainty_params* p);
 int coffee_analysis_set_uncertainty(coffee_analysis* h, const coffee_uncertainty_params* p);
 
+/* ---- variance-scaled exploration and noise pruning (the reference's
+ *      cpuctUtilityStdevScale and useNoisePruning, on in its match / analysis / GTP set-ups) ----
+ * Stdev factor (getFpuValueForChildrenAssumeVisited, searchexplorehelpers.cpp:256-277): the
+ * exploration scaling c * sqrt(total + 0.01) of a node's selection, and of the root's reduced
+ * play-selection weight, is multiplied by
+ *   factor = 1 + scale * (stdev / prior - 1)
+ *   stdev  = prior                                        if visits <= 0 or weight_sum <= 1
+ *          = sqrt(max(0, ((u^2 + prior^2) * prior_weight + max(utility_sq_avg, u^2) * weight_sum)
+ *                        / (prior_weight + weight_sum - 1) - u^2))        (u = utility_avg)
+ * Noise pruning (pruneNoiseWeight, searchupdatehelpers.cpp:423-467): a node's recompute scans
+ * its visited children in slot order; a child whose utility lies below the weighted average of
+ * the children before it and whose weight exceeds twice its prior's share of their weight loses
+ * min(cap, (weight - 2 share) * (1 - exp(-gap / utility_scale))); the node's weight_sum takes
+ * the scan's total, and the root's chosen-move subtract / prune amounts are 0.
+ * All in f32 with the search's deterministic exp.  Off (scale 0 and pruning 0, the default of
+ * all three engines), nothing changes. */
+typedef struct coffee_exploration_params {
+  int32_t use_noise_pruning;               /* 0 */
+  float noise_prune_utility_scale;         /* 0.15, range [0.001, 10] */
+  float noise_pruning_cap;                 /* FLT_MAX (1e50 in the reference), finite and >= 0 */
+  float cpuct_utility_stdev_prior;         /* 0.40, range [0, 10]; > 0 with scale > 0 */
+  float cpuct_utility_stdev_prior_weight;  /* 2.0,  range [0, 100] */
+  float cpuct_utility_stdev_scale;         /* 0 (the reference's set-ups: 0.85), range [0, 1] */
+} coffee_exploration_params;
+void coffee_exploration_params_default(coffee_exploration_params* p);
+/* The two formulas on the host (no device is touched), bit for bit what the search kernels
+ * compute.  COFFEE_EINVAL for out-of-range or non-finite parameters.
+ * _stdev_factor: *factor for a parent with the given statistics.
+ * _prune_noise_weight: the scan over n children in order (weight, utility from the parent's side,
+ * prior; priors below 1e-30 count as 1e-30): new_weight[n] and *new_total (either may be NULL).
+ * The scan runs whatever use_noise_pruning says.  With n <= 1 or a total of the weights <= 1e-5
+ * the weights come back unchanged and *new_total is their sum in order. */
+int coffee_explore_stdev_factor(const coffee_exploration_params* p, int64_t visits, float weight_sum,
+                                float utility_avg, float utility_sq_avg, float* factor);
+int coffee_prune_noise_weight(const coffee_exploration_params* p, int n, const float* weight, const float* utility,
+                              const float* prior, float* new_weight, float* new_total);
+/* Sets both mechanisms of an engine, under coffee_*_set_uncertainty's rules: only before the
+ * engine's first round (analysis: before the first query), COFFEE_EINVAL otherwise and for
+ * out-of-range or non-finite values, without touching the device.  side: -1 on an engine without
+ * per-side settings (one block for both nets), 0 / 1 on a match engine with them
+ * (coffee_match_create2, per_side); any other combination is COFFEE_EINVAL. */
+int coffee_selfplay_set_exploration(coffee_selfplay* h, const coffee_exploration_params* p);
+int coffee_analysis_set_exploration(coffee_analysis* h, const coffee_exploration_params* p);
+int coffee_match_set_exploration(coffee_match* h, int side, const coffee_exploration_params* p);
+/* Beside coffee_*_game_tree, in its breadth-first node order: priors [max_nodes][P], each node's
+ * child priors in slot order (the root's children carry the raw prior; its selection reads
+ * coffee_*_root_policy); next_prior / next_pos [max_nodes], each node's cached next expansion
+ * (-1 / 0xFFFF: none; unused at the root).  Any output may be NULL. */
+int coffee_selfplay_game_tree_priors(coffee_selfplay* h, int slot, int max_nodes, float* priors, float* next_prior,
+                                     int32_t* next_pos, int* n_nodes);
+int coffee_match_game_tree_priors(coffee_match* h, int slot, int max_nodes, float* priors, float* next_prior,
+                                  int32_t* next_pos, int* n_nodes);
+int coffee_analysis_game_tree_priors(coffee_analysis* h, int slot, int max_nodes, float* priors, float* next_prior,
+                                     int32_t* next_pos, int* n_nodes);
+
 /* ---- per-side match settings (the reference's `katago match`, whose search keys
  *      take a bot suffix, cpp/command/match.cpp) ----
  * A match engine whose two sides search with their own parameters and uncertainty weighting,

@@ -129,6 +129,13 @@ class UncertaintyParams(ctypes.Structure):
                 ("uncertainty_exponent", ctypes.c_float), ("uncertainty_max_weight", ctypes.c_float)]
 
 
+class ExplorationParams(ctypes.Structure):
+    """coffee_exploration_params: variance-scaled exploration and noise pruning."""
+    _fields_ = [("use_noise_pruning", ctypes.c_int32), ("noise_prune_utility_scale", ctypes.c_float),
+                ("noise_pruning_cap", ctypes.c_float), ("cpuct_utility_stdev_prior", ctypes.c_float),
+                ("cpuct_utility_stdev_prior_weight", ctypes.c_float), ("cpuct_utility_stdev_scale", ctypes.c_float)]
+
+
 class MatchSide(ctypes.Structure):
     """coffee_match_side: one side's search parameters and uncertainty weighting."""
     _fields_ = [("search", SearchParams), ("unc", UncertaintyParams)]
@@ -233,6 +240,9 @@ EXPORTS = [
     "coffee_match_create2", "coffee_match_elo",
     "coffee_analysis_set_root_options", "coffee_analysis_submit2", "coffee_analysis_drain2", "coffee_root_mask",
     "coffee_symmetry_move",
+    "coffee_exploration_params_default", "coffee_explore_stdev_factor", "coffee_prune_noise_weight",
+    "coffee_selfplay_set_exploration", "coffee_analysis_set_exploration", "coffee_match_set_exploration",
+    "coffee_selfplay_game_tree_priors", "coffee_match_game_tree_priors", "coffee_analysis_game_tree_priors",
 ]
 
 
@@ -352,6 +362,18 @@ def lib():
             L.coffee_analysis_drain2.argtypes = [c_p, c_i, c_p, c_p, c_p, c_p, c_p]
             L.coffee_root_mask.argtypes = [c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p]
             L.coffee_symmetry_move.argtypes = [c_i, c_i, c_i, c_i]
+        if hasattr(L, "coffee_explore_stdev_factor"):  # (absent in earlier builds run as A/B references)
+            L.coffee_exploration_params_default.argtypes = [c_p]
+            L.coffee_exploration_params_default.restype = None
+            L.coffee_explore_stdev_factor.argtypes = [c_p, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
+                                                      ctypes.c_float, c_p]
+            L.coffee_prune_noise_weight.argtypes = [c_p, c_i, c_p, c_p, c_p, c_p, c_p]
+            L.coffee_selfplay_set_exploration.argtypes = [c_p, c_p]
+            L.coffee_analysis_set_exploration.argtypes = [c_p, c_p]
+            L.coffee_match_set_exploration.argtypes = [c_p, c_i, c_p]
+            for f in (L.coffee_selfplay_game_tree_priors, L.coffee_match_game_tree_priors,
+                      L.coffee_analysis_game_tree_priors):
+                f.argtypes = [c_p, c_i, c_i, c_p, c_p, c_p, c_p]
         _lib = L
     return _lib
 
@@ -419,6 +441,62 @@ def uncertainty_weight(logit, params=None, **over):
     check(lib().coffee_uncertainty_weight(ctypes.byref(p), ctypes.c_float(float(logit)), ctypes.byref(err),
                                           ctypes.byref(w)))
     return np.float32(err.value), np.float32(w.value)
+
+
+def default_exploration_params(**over):
+    """coffee_exploration_params_default: both mechanisms off (stdev scale 0, no noise pruning),
+    stdev prior 0.40 with weight 2, utility scale 0.15, no cap (FLT_MAX).  The reference's match,
+    analysis and GTP set-ups run with cpuct_utility_stdev_scale=0.85 and use_noise_pruning=1."""
+    p = ExplorationParams()
+    lib().coffee_exploration_params_default(ctypes.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def _exploration_params(params, over):
+    p = default_exploration_params() if params is None else ExplorationParams.from_buffer_copy(params)
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def explore_stdev_factor(visits, weight_sum, utility_avg, utility_sq_avg, params=None, **over):
+    """The factor on a node's exploration scaling from the spread of its utility, as np.float32:
+    coffee_explore_stdev_factor, the host run of the search kernels' own sequence.  params: an
+    ExplorationParams (default: default_exploration_params()); keyword overrides on top."""
+    p = _exploration_params(params, over)
+    f = ctypes.c_float()
+    check(lib().coffee_explore_stdev_factor(ctypes.byref(p), int(visits), ctypes.c_float(float(weight_sum)),
+                                            ctypes.c_float(float(utility_avg)),
+                                            ctypes.c_float(float(utility_sq_avg)), ctypes.byref(f)))
+    return np.float32(f.value)
+
+
+def prune_noise_weight(weight, utility, prior, params=None, **over):
+    """(new_weight float32 [n], new_total np.float32) of the noise-pruning scan over n children in
+    order (their weights, utilities from the parent's side and priors): coffee_prune_noise_weight,
+    the host run of the search kernels' own sequence.  params / overrides as explore_stdev_factor."""
+    p = _exploration_params(params, over)
+    w = np.ascontiguousarray(weight, np.float32)
+    u = np.ascontiguousarray(utility, np.float32)
+    pr = np.ascontiguousarray(prior, np.float32)
+    if not (w.ndim == 1 and w.shape == u.shape == pr.shape):
+        raise ValueError("weight, utility and prior must be 1-D arrays of one length")
+    out = np.zeros_like(w)
+    tot = ctypes.c_float()
+    check(lib().coffee_prune_noise_weight(ctypes.byref(p), len(w), _ptr(w), _ptr(u), _ptr(pr), _ptr(out),
+                                          ctypes.byref(tot)))
+    return out, np.float32(tot.value)
+
+
+def _game_tree_priors(fn, h, P, slot, max_nodes):
+    priors = np.zeros((max_nodes, P), np.float32)
+    next_prior = np.zeros(max_nodes, np.float32)
+    next_pos = np.zeros(max_nodes, np.int32)
+    n = ctypes.c_int()
+    check(fn(h, slot, max_nodes, _ptr(priors), _ptr(next_prior), _ptr(next_pos), ctypes.byref(n)))
+    return priors[:n.value], next_prior[:n.value], next_pos[:n.value]
 
 
 def start_positions(positions):
@@ -896,6 +974,13 @@ class Selfplay:
         p = _uncertainty_params(params, over)
         check(lib().coffee_selfplay_set_uncertainty(self.h, ctypes.byref(p)))
 
+    def set_exploration(self, params=None, **over):
+        """Variance-scaled exploration and noise pruning (coffee_selfplay_set_exploration): an
+        ExplorationParams and / or its fields as keywords, e.g. use_noise_pruning=1,
+        cpuct_utility_stdev_scale=0.85.  Only before the engine's first round."""
+        p = _exploration_params(params, over)
+        check(lib().coffee_selfplay_set_exploration(self.h, ctypes.byref(p)))
+
     def set_start_positions(self, positions, prob, turn_weight_lambda=0.0, start_policy_init_area_prop=0.0):
         """Start positions (coffee_selfplay_set_start_positions): games that start from now on
         begin with probability `prob` from a sample of `positions` (see start_positions()),
@@ -1000,6 +1085,11 @@ class Selfplay:
         check(lib().coffee_selfplay_game_tree(self.h, slot, max_nodes, _ptr(nodes), _ptr(edges), ctypes.byref(n)))
         return nodes[:n.value], edges[:n.value]
 
+    def game_tree_priors(self, slot, max_nodes=4096):
+        """(priors [n][P], next_prior [n], next_pos [n]) beside game_tree, in its node order: each
+        node's child priors in slot order and its cached next expansion (coffee_selfplay_game_tree_priors)."""
+        return _game_tree_priors(lib().coffee_selfplay_game_tree_priors, self.h, self.P, slot, max_nodes)
+
     def root_policy(self, slot):
         out = np.zeros(self.P, np.float32)
         check(lib().coffee_selfplay_root_policy(self.h, slot, _ptr(out)))
@@ -1101,6 +1191,13 @@ class Match:
         p = _uncertainty_params(params, over)
         check(lib().coffee_match_set_uncertainty(self.h, ctypes.byref(p)))
 
+    def set_exploration(self, params=None, side=-1, **over):
+        """Variance-scaled exploration and noise pruning (coffee_match_set_exploration): an
+        ExplorationParams and / or its fields as keywords.  side: -1 on an engine without per-side
+        settings, 0 / 1 on one with them.  Only before the engine's first round."""
+        p = _exploration_params(params, over)
+        check(lib().coffee_match_set_exploration(self.h, int(side), ctypes.byref(p)))
+
     def set_start_positions(self, positions, prob, turn_weight_lambda=0.0, start_policy_init_area_prop=0.0):
         """Start positions (coffee_match_set_start_positions), as Selfplay.set_start_positions:
         opening variety that depends on neither net's policy."""
@@ -1155,6 +1252,11 @@ class Match:
         n = ctypes.c_int()
         check(lib().coffee_match_game_tree(self.h, slot, max_nodes, _ptr(nodes), _ptr(edges), ctypes.byref(n)))
         return nodes[:n.value], edges[:n.value]
+
+    def game_tree_priors(self, slot, max_nodes=4096):
+        """(priors [n][P], next_prior [n], next_pos [n]) beside game_tree, in its node order: each
+        node's child priors in slot order and its cached next expansion (coffee_match_game_tree_priors)."""
+        return _game_tree_priors(lib().coffee_match_game_tree_priors, self.h, self.P, slot, max_nodes)
 
     def root_policy(self, slot):
         out = np.zeros(self.P, np.float32)
@@ -1254,6 +1356,13 @@ class Analysis:
         p = _uncertainty_params(params, over)
         check(lib().coffee_analysis_set_uncertainty(self.h, ctypes.byref(p)))
 
+    def set_exploration(self, params=None, **over):
+        """Variance-scaled exploration and noise pruning (coffee_analysis_set_exploration): an
+        ExplorationParams and / or its fields as keywords, e.g. use_noise_pruning=1,
+        cpuct_utility_stdev_scale=0.85.  Only before the engine's first round and query."""
+        p = _exploration_params(params, over)
+        check(lib().coffee_analysis_set_exploration(self.h, ctypes.byref(p)))
+
     def sync(self):
         check(lib().coffee_analysis_sync(self.h))
 
@@ -1335,6 +1444,11 @@ class Analysis:
         n = ctypes.c_int()
         check(lib().coffee_analysis_game_tree(self.h, slot, max_nodes, _ptr(nodes), _ptr(edges), ctypes.byref(n)))
         return nodes[:n.value], edges[:n.value]
+
+    def game_tree_priors(self, slot, max_nodes=4096):
+        """(priors [n][P], next_prior [n], next_pos [n]) beside game_tree, in its node order: each
+        node's child priors in slot order and its cached next expansion (coffee_analysis_game_tree_priors)."""
+        return _game_tree_priors(lib().coffee_analysis_game_tree_priors, self.h, self.P, slot, max_nodes)
 
     def root_policy(self, slot):
         out = np.zeros(self.P, np.float32)

@@ -1,6 +1,7 @@
 // C ABI (include/katacoffee.h): argument checking, error capture, dispatch.
 // No C++ exception crosses this boundary; failures return COFFEE_E* with the
 // message in coffee_last_error().
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -886,6 +887,103 @@ int coffee_analysis_set_uncertainty(coffee_analysis* h, const coffee_uncertainty
   return guarded([&] {
     need(h && h->eng && p, "NULL argument");
     h->eng->setUncertainty(*p);
+  });
+}
+
+// ---- variance-scaled exploration and noise pruning (explore.h: the sequences the kernels run) ----
+
+void coffee_exploration_params_default(coffee_exploration_params* p) {
+  if(!p)
+    return;
+  // searchparams.cpp (both off); the other fields as setup.cpp:453-470, :520-537 load them
+  p->use_noise_pruning = 0;
+  p->noise_prune_utility_scale = 0.15f;
+  p->noise_pruning_cap = FLT_MAX;
+  p->cpuct_utility_stdev_prior = 0.40f;
+  p->cpuct_utility_stdev_prior_weight = 2.0f;
+  p->cpuct_utility_stdev_scale = 0.0f;
+}
+
+int coffee_explore_stdev_factor(const coffee_exploration_params* p, int64_t visits, float weight_sum,
+                                float utility_avg, float utility_sq_avg, float* factor) {
+  return guarded([&] {
+    need(p && factor, "NULL argument");
+    const Expl e = toExpl(*p);
+    const uint32_t v = visits <= 0 ? 0u : (visits > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)visits);
+    *factor = exploreStdevFactor(e, v, weight_sum, utility_avg, utility_sq_avg);
+  });
+}
+
+int coffee_prune_noise_weight(const coffee_exploration_params* p, int n, const float* weight, const float* utility,
+                              const float* prior, float* new_weight, float* new_total) {
+  return guarded([&] {
+    need(p != nullptr && n >= 0, "NULL argument or n < 0");
+    need(n == 0 || (weight && utility && prior), "NULL argument");
+    const Expl e = toExpl(*p);
+    float total = 0.0f;
+    for(int i = 0; i < n; i++)
+      total = total + weight[i];
+    if(!pruneNoiseApplies(n, total)) {  // (the scan itself: use_noise_pruning is not consulted)
+      if(new_weight)
+        for(int i = 0; i < n; i++)
+          new_weight[i] = weight[i];
+      if(new_total)
+        *new_total = total;
+      return;
+    }
+    PruneScan sc{0.0f, 0.0f, 0.0f};
+    for(int i = 0; i < n; i++) {
+      const float nw = pruneNoiseStep(e, sc, weight[i], utility[i], prior[i]);
+      if(new_weight)
+        new_weight[i] = nw;
+    }
+    if(new_total)
+      *new_total = sc.wSum;
+  });
+}
+
+int coffee_selfplay_set_exploration(coffee_selfplay* h, const coffee_exploration_params* p) {
+  return guarded([&] {
+    need(h && h->eng && p, "NULL argument");
+    h->eng->setExploration(-1, *p);
+  });
+}
+
+int coffee_analysis_set_exploration(coffee_analysis* h, const coffee_exploration_params* p) {
+  return guarded([&] {
+    need(h && h->eng && p, "NULL argument");
+    h->eng->setExploration(-1, *p);
+  });
+}
+
+int coffee_match_set_exploration(coffee_match* h, int side, const coffee_exploration_params* p) {
+  return guarded([&] {
+    need(h && h->eng && p, "NULL argument");
+    h->eng->setExploration(side, *p);
+  });
+}
+
+int coffee_selfplay_game_tree_priors(coffee_selfplay* h, int slot, int max_nodes, float* priors, float* next_prior,
+                                     int32_t* next_pos, int* n_nodes) {
+  return guarded([&] {
+    need(h && h->eng && n_nodes, "NULL argument");
+    *n_nodes = h->eng->gameTreePriors(slot, max_nodes, priors, next_prior, next_pos);
+  });
+}
+
+int coffee_match_game_tree_priors(coffee_match* h, int slot, int max_nodes, float* priors, float* next_prior,
+                                  int32_t* next_pos, int* n_nodes) {
+  return guarded([&] {
+    need(h && h->eng && n_nodes, "NULL argument");
+    *n_nodes = h->eng->gameTreePriors(slot, max_nodes, priors, next_prior, next_pos);
+  });
+}
+
+int coffee_analysis_game_tree_priors(coffee_analysis* h, int slot, int max_nodes, float* priors, float* next_prior,
+                                     int32_t* next_pos, int* n_nodes) {
+  return guarded([&] {
+    need(h && h->eng && n_nodes, "NULL argument");
+    *n_nodes = h->eng->gameTreePriors(slot, max_nodes, priors, next_prior, next_pos);
   });
 }
 

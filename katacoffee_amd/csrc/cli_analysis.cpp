@@ -294,6 +294,7 @@ int analysisMain(int argc, char** argv) {
   Settings s;
   coffee_analysis_params_default(&s.sp);
   coffee_uncertainty_params_default(&s.unc);
+  coffee_exploration_params_default(&s.ex);
   int slots = 64, pvLen = 15;  // analysis_example.cfg: analysisPVLen 15
   try {
     applyConfig(kv, s);
@@ -328,6 +329,7 @@ int analysisMain(int argc, char** argv) {
   Service sv;
   must(coffee_analysis_create(&c, &sv.h), "create analysis engine");
   must(coffee_analysis_set_uncertainty(sv.h, &s.unc), "set uncertainty");
+  must(coffee_analysis_set_exploration(sv.h, &s.ex), "set exploration");
   // the policy travels with every result: a query's includePolicy prints it, and the symmetry
   // copies read the legal moves off it
   const coffee_analysis_root_options ro{s.rootSymmetryPruning, 1};

@@ -4,7 +4,9 @@
 // (tests/san, tests/test_sanitizers.py) checks the same code the CLI runs.
 #pragma once
 #include <algorithm>
+#include <cfloat>
 #include <cstdint>
+#include <cstdlib>
 #include <fstream>
 #include <map>
 #include <stdexcept>
@@ -61,6 +63,10 @@ struct Settings {
   // off) by the command before applyConfig; off unless the config turns it on, for all three
   // commands (the reference's loader defaults it on for analysis, GTP and match, setup.cpp:539-562)
   coffee_uncertainty_params unc;
+  // cpuctUtilityStdevScale, useNoisePruning & co: like unc, the library's defaults
+  // (coffee_exploration_params_default: both off) unless the config turns them on, for all four
+  // commands (the reference's loader defaults them on for analysis, GTP and match, setup.cpp:453-537)
+  coffee_exploration_params ex = {0, 0.15f, FLT_MAX, 0.40f, 2.0f, 0.0f};
   // rootSymmetryPruning (`katago analysis` only): off unless the config turns it on -- the
   // reference's loader defaults it on for analysis and GTP (setup.cpp:639-644)
   int32_t rootSymmetryPruning = 0;
@@ -216,6 +222,33 @@ inline void applySearchConfig(const ConfigReader& r, coffee_search_params& p, co
   r.getfIn("uncertaintyMaxWeight", unc.uncertainty_max_weight, 1.0f, 100.0f);
 }
 
+// The six exploration keys onto ex, with the reference's ranges (setup.cpp:453-470, :520-537;
+// r.suffix: the bot of `katago match`).  A noisePruningCap above FLT_MAX (the reference's default
+// is 1e50) is stored as FLT_MAX.
+inline void applyExplorationConfig(const ConfigReader& r, coffee_exploration_params& ex) {
+  r.getfIn("cpuctUtilityStdevPrior", ex.cpuct_utility_stdev_prior, 0.0f, 10.0f);
+  r.getfIn("cpuctUtilityStdevPriorWeight", ex.cpuct_utility_stdev_prior_weight, 0.0f, 100.0f);
+  r.getfIn("cpuctUtilityStdevScale", ex.cpuct_utility_stdev_scale, 0.0f, 1.0f);
+  r.getb("useNoisePruning", ex.use_noise_pruning);
+  r.getfIn("noisePruneUtilityScale", ex.noise_prune_utility_scale, 0.001f, 10.0f);
+  {
+    std::string n;
+    auto it = r.find("noisePruningCap", n);
+    if(it != r.kv.end()) {
+      char* end = nullptr;
+      const double c = strtod(it->second.c_str(), &end);
+      if(it->second.empty() || end != it->second.c_str() + it->second.size())
+        throw ConfigReader::bad(n, it->second);
+      if(!(c >= 0.0))
+        throw std::invalid_argument("config key " + n + ": value " + it->second + " outside [0, inf)");
+      ex.noise_pruning_cap = c > (double)FLT_MAX ? FLT_MAX : (float)c;
+    }
+  }
+  if(ex.cpuct_utility_stdev_prior == 0.0f && ex.cpuct_utility_stdev_scale > 0.0f)
+    throw std::invalid_argument("config key cpuctUtilityStdevPrior" + r.suffix +
+                                ": must be > 0 with cpuctUtilityStdevScale > 0");
+}
+
 inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& s) {
   const ConfigReader r{kv, ""};
   auto it = kv.find("bSizes");
@@ -248,6 +281,7 @@ inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& 
       throw std::invalid_argument("nnPrecision must be auto, corrected, accurate, fast or fastLayered");
   }
   applySearchConfig(r, s.sp, s.unc);
+  applyExplorationConfig(r, s.ex);
   r.getb("rootSymmetryPruning", s.rootSymmetryPruning);
   // start positions (play.cpp:186-196 getters: the same ranges)
   r.gets("startPosesFromSgfDir", s.startPos.sgfDirs);
@@ -266,10 +300,12 @@ struct MatchBot {
   std::string name, model;
   coffee_search_params sp;
   coffee_uncertainty_params unc;
+  coffee_exploration_params ex;  // the six exploration keys, per bot like every search key
 };
 
 inline void applyMatchBots(const std::map<std::string, std::string>& kv, const coffee_search_params& defSp,
-                           const coffee_uncertainty_params& defUnc, MatchBot bots[2]) {
+                           const coffee_uncertainty_params& defUnc, const coffee_exploration_params& defEx,
+                           MatchBot bots[2]) {
   {
     auto it = kv.find("numBots");
     if(it != kv.end() && ConfigReader::parseInt("numBots", it->second) != 2)
@@ -281,11 +317,21 @@ inline void applyMatchBots(const std::map<std::string, std::string>& kv, const c
     bots[i].sp = defSp;
     bots[i].unc = defUnc;
     applySearchConfig(r, bots[i].sp, bots[i].unc);
+    bots[i].ex = defEx;
+    applyExplorationConfig(r, bots[i].ex);
     bots[i].name = "bot" + std::to_string(i);
     r.gets("botName", bots[i].name);
     bots[i].model.clear();
     r.gets("nnModelFile", bots[i].model);
   }
+}
+
+// (exploration from the library's defaults: both mechanisms off)
+inline void applyMatchBots(const std::map<std::string, std::string>& kv, const coffee_search_params& defSp,
+                           const coffee_uncertainty_params& defUnc, MatchBot bots[2]) {
+  coffee_exploration_params defEx;
+  coffee_exploration_params_default(&defEx);
+  applyMatchBots(kv, defSp, defUnc, defEx, bots);
 }
 
 }  // namespace kccli

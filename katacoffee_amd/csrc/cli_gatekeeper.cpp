@@ -107,6 +107,7 @@ bool gateOnce(const Settings& s, int gamesPerGating, const Dirs& d, bool autoRej
   coffee_match* h = nullptr;
   must(coffee_match_create(&c, &h), "create match engine");
   must(coffee_match_set_uncertainty(h, &s.unc), "set uncertainty");  // one setting for both nets
+  must(coffee_match_set_exploration(h, -1, &s.ex), "set exploration");  // likewise
   if(s.unc.use_uncertainty)
     logf("gatekeeper: uncertainty weighting on for both nets: coeff %g, exponent %g, max weight %g",
          s.unc.uncertainty_coeff, s.unc.uncertainty_exponent, s.unc.uncertainty_max_weight);
@@ -232,6 +233,7 @@ int gatekeeperMain(int argc, char** argv) {
   s.games = 128;  // gatekeeper1.cfg numGameThreads
   coffee_match_params_default(&s.sp);
   coffee_uncertainty_params_default(&s.unc);
+  coffee_exploration_params_default(&s.ex);
   int gamesPerGating = 200;  // gatekeeper1.cfg numGamesPerGating
   try {
     applyConfig(kv, s);

@@ -138,13 +138,15 @@ int matchMain(int argc, char** argv) {
   s.games = 128;
   coffee_match_params_default(&s.sp);
   coffee_uncertainty_params_default(&s.unc);
+  coffee_exploration_params_default(&s.ex);
+  const coffee_exploration_params defEx = s.ex;
   const coffee_search_params defSp = s.sp;
   const coffee_uncertainty_params defUnc = s.unc;
   MatchBot bots[2];
   int N = 0, logEvery = 50;
   try {
     applyConfig(kv, s);  // geometry, threads, cache, precision, start positions; s.sp: the game-level settings
-    applyMatchBots(kv, defSp, defUnc, bots);
+    applyMatchBots(kv, defSp, defUnc, defEx, bots);
     N = intKey(kv, "numGamesTotal", 0, true);
     logEvery = intKey(kv, "logGamesEvery", 50, false);
   } catch(const std::invalid_argument& e) {
@@ -216,6 +218,13 @@ int matchMain(int argc, char** argv) {
               : "match: two model files: each bot's net has its own launch and cache");
   coffee_match* h = nullptr;
   must(coffee_match_create2(&c, &o, &h), "create match engine");
+  for(int i = 0; i < 2; i++) {
+    must(coffee_match_set_exploration(h, i, &bots[i].ex), "set exploration");
+    if(bots[i].ex.use_noise_pruning || bots[i].ex.cpuct_utility_stdev_scale != 0.0f)
+      logf("match: bot %d: cpuct stdev scale %g (prior %g, weight %g), noise pruning %s", i,
+           bots[i].ex.cpuct_utility_stdev_scale, bots[i].ex.cpuct_utility_stdev_prior,
+           bots[i].ex.cpuct_utility_stdev_prior_weight, bots[i].ex.use_noise_pruning ? "on" : "off");
+  }
   if(!startPos.empty())
     must(coffee_match_set_start_positions(h, startPos.data(), (int)startPos.size(), &s.startPos.params),
          "set start positions");

@@ -206,6 +206,7 @@ static void runGpu(int gpu, int server, int perGpu, int slot, int share, const S
   coffee_selfplay* h = nullptr;
   check(coffee_selfplay_create(&c, &h), "create engine");
   check(coffee_selfplay_set_uncertainty(h, &s.unc), "set uncertainty");
+  check(coffee_selfplay_set_exploration(h, &s.ex), "set exploration");
   if(s.unc.use_uncertainty)
     logf("gpu %d.%d: uncertainty weighting on: coeff %g, exponent %g, max weight %g", gpu, server,
          s.unc.uncertainty_coeff, s.unc.uncertainty_exponent, s.unc.uncertainty_max_weight);
@@ -368,6 +369,7 @@ int main(int argc, char** argv) {
   Settings s;
   coffee_search_params_default(&s.sp);
   coffee_uncertainty_params_default(&s.unc);
+  coffee_exploration_params_default(&s.ex);
   try {
     applyConfig(kv, s);
   } catch(const std::exception& e) {

@@ -26,6 +26,7 @@
 #include "rootmask.h"
 #include "startpos.h"
 #include "uncertainty.h"
+#include "explore.h"
 
 namespace kc {
 
@@ -410,6 +411,11 @@ struct SearchDev {
   DPtr<coffee_analysis_root_info> aRootInfo;     // [aCap] beside aRes
   DPtr<float> aPolicy;                           // [aCap][P] beside aRes (null: no policy output)
   int32_t aPrune, aPad;
+  // variance-scaled exploration and noise pruning (coffee_*_set_exploration; explore.h, DESIGN.md
+  // 8g), read by the EXPL kernel instantiations only: ex beside unc, ex1 beside unc1 (side 1 of a
+  // per-side match engine; a copy of ex on every other engine).  Off: the launchers never pick
+  // those instantiations.
+  Expl ex, ex1;
 };
 
 // Match play: the candidate (net 1) plays black (player 1) in game number n of global
@@ -451,6 +457,11 @@ void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st);  // 
 // to the device, reports the listed searches and lets the idle slots pop queued queries)
 void launchGameTree(const SearchDev* dd, int slot, int maxNodes, uint32_t* nodesOut, uint32_t* edgesOut,
                     int32_t* count, hipStream_t st);
+// The priors beside launchGameTree's export, same node order: priorsOut [maxNodes][P] f32 bits
+// (child priors in slot order), nextOut [maxNodes][2] (nextPrior bits, nextPos); order
+// [maxNodes] is scratch.
+void launchGameTreePriors(const SearchDev* dd, int slot, int maxNodes, uint32_t* priorsOut, uint32_t* nextOut,
+                          int32_t* order, int32_t* count, hipStream_t st) __attribute__((weak));
 // Dynamic LDS bytes the commit kernel needs for node_cap `cap`.
 size_t commitLdsBytes(int cap);
 // Replays n start-position samples (device array) with the device rules at geometry T (device

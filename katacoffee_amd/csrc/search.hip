@@ -208,6 +208,9 @@ KC_D void bindGame(GV& v, const GameDev& s) {
   v.setEdgeSel(s.edgeSel);
 }
 
+// The exploration block (explore.h) of the view's side: beside unc / unc1.
+KC_D const Expl& explOf(const GV& v) { return v.unc == &v.d.unc1 ? v.d.ex1 : v.d.ex; }
+
 // MATCH with per-side settings: the visit limit of the search about to start is the next
 // mover's (setMoveLimits gave side 0's; match play has no cheap or reduced searches).
 template <bool MATCH>
@@ -447,8 +450,16 @@ KC_D float cdfT(const DTables& T, float z) {
 // computed, so the path child's record and (when the two levels share an SVB entry)
 // the SVB sums can be stale: computeLevel takes both from the level below (`below`),
 // which is exactly what the sequential order would read.
+// (EXPL, the kernels' exploration flag -- DESIGN.md 8g: the noise-pruning scan needs each
+// child's prior, which only those instantiations carry)
+template <int NI, bool EXPL>
+struct PathPriors {};
 template <int NI>
-struct PathLevel {
+struct PathPriors<NI, true> {
+  float epr[NI];  // the parent's prior of the child's move (root: the noised root policy)
+};
+template <int NI, bool EXPL = false>
+struct PathLevel : PathPriors<NI, EXPL> {
   int ni, slot, k, nextPla, svbEntry;
   uint32_t ebase;
   float nnWin, nnLoss, nnWeight, lastSvbDelta, lastSvbWeight;
@@ -465,8 +476,8 @@ struct LevelOut {
   int64_t svbD, svbW;
 };
 
-template <int NI>
-KC_D void loadLevel(const GV& v, int ni, int slot, PathLevel<NI>& L) {
+template <int NI, bool EXPL>
+KC_D void loadLevel(const GV& v, int ni, int slot, PathLevel<NI, EXPL>& L) {
   const Node nd = v.nodes()[ni];
   const Edge* E = v.inlineEdges(ni);
   // the first SPEC_EDGES slots speculatively with the record (slots past numChildren
@@ -488,8 +499,8 @@ KC_D void loadLevel(const GV& v, int ni, int slot, PathLevel<NI>& L) {
   L.visits0 = nd.visits;
 }
 
-template <int NI>
-KC_D void loadKids(const GV& v, const GameDev& s, PathLevel<NI>& L) {
+template <int NI, bool EXPL>
+KC_D void loadKids(const GV& v, const GameDev& s, PathLevel<NI, EXPL>& L) {
   const SP& sp = *v.sp;
   const NodeEdges E = v.edges(L.ni, L.ebase);
   const Node* NS = v.nodes();
@@ -498,6 +509,8 @@ KC_D void loadKids(const GV& v, const GameDev& s, PathLevel<NI>& L) {
     const int i = v.lane + 64 * j;
     L.cv[j] = 0;
     L.cws[j] = L.cwsq[j] = L.cu[j] = L.cusq[j] = L.cwl[j] = 0.0f;
+    if constexpr(EXPL)
+      L.epr[j] = 0.0f;
     if(j > 0 || i >= SPEC_EDGES)
       L.ech[j] = L.evis[j] = 0u;
     if(i < L.k) {
@@ -505,6 +518,11 @@ KC_D void loadKids(const GV& v, const GameDev& s, PathLevel<NI>& L) {
         const Edge e = E[i];
         L.ech[j] = e.child;
         L.evis[j] = e.visits;
+      }
+      if constexpr(EXPL) {
+        // the edge again for its prior and move (the speculative read kept neither)
+        const Edge e = E[i];
+        L.epr[j] = L.ni == s.rootIdx ? v.rootNoised()[e.move] : e.prior;
       }
       const Node& c = NS[L.ech[j]];
       L.cv[j] = c.visits;
@@ -526,8 +544,8 @@ KC_D void loadKids(const GV& v, const GameDev& s, PathLevel<NI>& L) {
 // issueNext() issues the next levels' loads; it runs right after this level's t-CDF
 // table reads, the last loads the level waits on (vmcnt counts in issue order, so a
 // wait on a load also waits on every older one).
-template <int NI, class F>
-KC_D LevelOut computeLevel(const GV& v, const GameDev& s, PathLevel<NI>& L, const LevelOut& below, bool haveBelow,
+template <int NI, bool EXPL, class F>
+KC_D LevelOut computeLevel(const GV& v, const GameDev& s, PathLevel<NI, EXPL>& L, const LevelOut& below, bool haveBelow,
                            int numVisitsToAdd, bool isRoot, F&& issueNext) {
   const SP& sp = *v.sp;
   const unsigned long long tLoads = SPROF_NOW();
@@ -588,9 +606,34 @@ KC_D LevelOut computeLevel(const GV& v, const GameDev& s, PathLevel<NI>& L, cons
   }
   maxW = waveMax(maxW);
   const float origTotal = tsum<NI>(wAdj, k, v.lane);
-  const float currentTotal = origTotal;
+  float currentTotal = origTotal;
+  bool pruning = false;
+  if constexpr(EXPL) {
+    // noise pruning (explore.h): the serial scan over the good children in slot order, run by
+    // every lane on broadcasts of the slot's values; the slot's own lane keeps the new weight.
+    // currentTotal is the scan's own sum.
+    const Expl& ex = explOf(v);
+    pruning = ex.noisePruning != 0;
+    if(pruning && pruneNoiseApplies(numGood, origTotal)) {
+      PruneScan sc{0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for(int j = 0; j < NI; j++) {
+        const int cnt = k - 64 * j < 64 ? k - 64 * j : 64;  // uniform
+        const uint64_t gm = ballot(good[j]);
+        for(int l = 0; l < cnt; l++) {
+          if(!((gm >> l) & 1ull))
+            continue;
+          const float old = bcastLaneF(wAdj[j], l), u = bcastLaneF(selfU[j], l), pr = bcastLaneF(L.epr[j], l);
+          const float nw = pruneNoiseStep(ex, sc, old, u, pr);
+          if(v.lane == l)
+            wAdj[j] = nw;
+        }
+      }
+      currentTotal = sc.wSum;
+    }
+  }
   float amountToSubtract = 0.0f, amountToPrune = 0.0f;
-  if(isRoot && sp.rootNoise) {
+  if(isRoot && sp.rootNoise && !pruning) {
     amountToSubtract = fminf(sp.moveSubtract, maxW / 64.0f);
     amountToPrune = fminf(sp.movePrune, maxW / 64.0f);
   }
@@ -745,7 +788,7 @@ KC_D LevelOut computeLevel(const GV& v, const GameDev& s, PathLevel<NI>& L, cons
 // first edges, then child records) and the record of level j-2 are issued before
 // level j is computed; with more than two items per lane (register budget) the
 // levels run one at a time.
-template <int NI>
+template <int NI, bool EXPL = false>
 KC_D void backupPath(const GV& v, const GameDev& s, int pathLen, NStats leaf, bool haveLeaf) {
   const int32_t* pn = v.pathNode();
   const int32_t* ps = v.pathSlot();
@@ -764,30 +807,30 @@ KC_D void backupPath(const GV& v, const GameDev& s, int pathLen, NStats leaf, bo
   if constexpr(NI > 2) {
     // wide levels (7x7, 9x9): one level at a time
     for(; j >= 0; j--) {
-      PathLevel<NI> cur;
-      loadLevel<NI>(v, nodeAt(j), slotAt(j), cur);
-      loadKids<NI>(v, s, cur);
-      below = computeLevel<NI>(v, s, cur, below, haveBelow, 1, cur.ni == s.rootIdx, [] {});
+      PathLevel<NI, EXPL> cur;
+      loadLevel<NI, EXPL>(v, nodeAt(j), slotAt(j), cur);
+      loadKids<NI, EXPL>(v, s, cur);
+      below = computeLevel<NI, EXPL>(v, s, cur, below, haveBelow, 1, cur.ni == s.rootIdx, [] {});
       haveBelow = true;
     }
     return;
   }
-  PathLevel<NI> cur, nxt;
-  loadLevel<NI>(v, nodeAt(j), slotAt(j), cur);
+  PathLevel<NI, EXPL> cur, nxt;
+  loadLevel<NI, EXPL>(v, nodeAt(j), slotAt(j), cur);
   if(j > 0)
-    loadLevel<NI>(v, nodeAt(j - 1), slotAt(j - 1), nxt);
-  loadKids<NI>(v, s, cur);
+    loadLevel<NI, EXPL>(v, nodeAt(j - 1), slotAt(j - 1), nxt);
+  loadKids<NI, EXPL>(v, s, cur);
   for(; j >= 0; j--) {
-    PathLevel<NI> nn;
+    PathLevel<NI, EXPL> nn;
     // the child records of the level above and the record two levels up, issued
     // while this level is computed
     auto issueNext = [&] {
       if(j > 0)
-        loadKids<NI>(v, s, nxt);
+        loadKids<NI, EXPL>(v, s, nxt);
       if(j > 1)
-        loadLevel<NI>(v, nodeAt(j - 2), slotAt(j - 2), nn);
+        loadLevel<NI, EXPL>(v, nodeAt(j - 2), slotAt(j - 2), nn);
     };
-    below = computeLevel<NI>(v, s, cur, below, haveBelow, 1, cur.ni == s.rootIdx, issueNext);
+    below = computeLevel<NI, EXPL>(v, s, cur, below, haveBelow, 1, cur.ni == s.rootIdx, issueNext);
     haveBelow = true;
     if(j > 0) {
       cur = nxt;
@@ -824,7 +867,7 @@ KC_D float exploreScaling(const SP& sp, float totalChildWeight) {
 // oracle selectBest (selectBestChildToDescend searchexplorehelpers.cpp:304-451)
 // Also returns the chosen existing child's edge and the child's visits and flags,
 // broadcast from the lane that holds them (no reload of either after the choice).
-template <int NI>
+template <int NI, bool EXPL = false>
 KC_D int selectBest(const GV& v, int ni, const Node& n, const float* pol, bool isRoot, int& newPos,
                     uint32_t* hasBits, const Edge& e0, Edge& ce, uint32_t& cVisits, uint32_t& cFlags) {
   const SP& sp = *v.sp;
@@ -873,7 +916,9 @@ KC_D int selectBest(const GV& v, int ni, const Node& n, const float* pol, bool i
   const float probMass = tsum<NI>(probs, k, v.lane);
   const float total = tsum<NI>(cw, k, v.lane);
   const float fpu = fpuValue(sp, n, pla, isRoot, probMass);
-  const float scaling = exploreScaling(sp, total);
+  float scaling = exploreScaling(sp, total);
+  if constexpr(EXPL)
+    scaling = scaling * exploreStdevFactor(explOf(v), n.visits, n.weightSum, n.utilityAvg, n.utilitySqAvg);
   float best = -__builtin_inff();
   int bestIdx = BIG;
 #pragma unroll
@@ -983,7 +1028,7 @@ KC_D void nextExpansion(const GV& v, const float (&pv)[NI], float curPrior, int 
 
 // oracle descend (playoutDescend search.cpp:936-1165, allocateOrFindNode :704-759,
 // maybeCatchUpEdgeVisits :1169-1207)
-template <int NI>
+template <int NI, bool EXPL = false>
 KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* LDS [P] */) {
   constexpr bool W1 = W1_OF<NI>;
   const SP& sp = *v.sp;
@@ -1045,8 +1090,8 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
     // a node with at most 64 children (every non-root level in practice, the root until
     // its 65th child) takes the one-item form: an empty second item adds nothing to the
     // sums and never wins the (value, index) argmax, so the results are the same
-    int slot = n.numChildren <= 64 ? selectBest<1>(v, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags)
-                                   : selectBest<NI>(v, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags);
+    int slot = n.numChildren <= 64 ? selectBest<1, EXPL>(v, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags)
+                                   : selectBest<NI, EXPL>(v, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags);
     SPROF_ADD(5, SPROF_NOW() - tSel);
     (void)tSel;
     if(slot < 0) {
@@ -1294,7 +1339,7 @@ KC_D void finishSelect(const GV& v, GameDev& s, DRng& rng) {
 
 // One game's selection.  s: the game's LDS copy, already holding its state when `loaded`
 // (the fused kernel's backup just ran; every path below then stores it).  rootPol: LDS [MAX_P].
-template <int NI, bool MATCH = false>
+template <int NI, bool MATCH = false, bool EXPL = false>
 KC_D void selectBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bool loaded, bool fused,
                      uint32_t* hasBits, float* rootPol) {
   GV v(d, T, g);
@@ -1368,7 +1413,7 @@ KC_D void selectBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
     s.leafSym = (int)((s.syms >> (4 * s.rootK)) & 15u);
     s.leaf = s.root;
   } else {
-    descend<NI>(v, s, hasBits, rootPol);
+    descend<NI, EXPL>(v, s, hasBits, rootPol);
     if(s.leafKind == LEAF_NN && d.cacheOn)
       cacheLookup<NI, MATCH>(v, s, fused);
   }
@@ -1386,7 +1431,7 @@ KC_D void selectBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   SPROF_FLUSH();
 }
 
-template <int NI, bool MATCH = false>
+template <int NI, bool MATCH = false, bool EXPL = false>
 __global__ void __launch_bounds__(64, NI <= 2 ? 4 : 2) kSelect(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp,
                                                                 int resetCommit) {
   const SearchDev& d = *dp;
@@ -1400,7 +1445,7 @@ __global__ void __launch_bounds__(64, NI <= 2 ? 4 : 2) kSelect(const SearchDev* 
   __shared__ uint32_t hasBits[(MAX_P + 31) / 32];
   __shared__ GameDev s;
   __shared__ float rootPol[MAX_P];
-  selectBody<NI, MATCH>(d, *Tp, g, s, false, false, hasBits, rootPol);
+  selectBody<NI, MATCH, EXPL>(d, *Tp, g, s, false, false, hasBits, rootPol);
 }
 
 // The selections a fused kernel left pending: the cache slot is final now (every backup
@@ -1740,7 +1785,10 @@ KC_D const T* uniformConst(const T* p) {
   asm volatile("" : "+s"(q));
   return (const T*)q;
 }
-template <int NI, bool MATCH = false>
+// (EXPL: nothing here reads it; it gives each round kernel the out-of-line copy of its own
+// instantiation family, as MATCH does, so a copy's callers -- and with them what the compiler
+// propagates into it -- stay the ones it had before the exploration kernels existed)
+template <int NI, bool MATCH = false, bool EXPL = false>
 __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, int g, GameDev* gs, float* scratch) {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   const SearchDev& d = *uniformConst(dp);
@@ -1839,7 +1887,7 @@ __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, in
 // stored -- selectBody stores it on every path).
 // fused (kBackupSelect): a cache-slot winner leaves the slot's tag set -- the selections
 // running beside it treat the slot as being written -- and kResolve clears it.
-template <int NI, bool MATCH = false>
+template <int NI, bool MATCH = false, bool EXPL = false>
 KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bool fused, float* scratch) {
   if(d.nnDefer[g])  // a deferred leaf is backed up in a later round
     return false;
@@ -1858,7 +1906,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   const float* o = d.nnOut + (size_t)s.nnSlot * (P + 4);
   bool needCommit = false;
   if(s.leafKind == LEAF_INIT || s.leafKind == LEAF_FORK || s.leafKind == LEAF_SIDE || s.leafKind == LEAF_ROOTEVAL) {
-    needCommit = rareLeaf<NI, MATCH>(&d, &T, g, &s, scratch);
+    needCommit = rareLeaf<NI, MATCH, EXPL>(&d, &T, g, &s, scratch);
   } else {
     NStats leafSt{0u, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     bool haveLeaf = false;
@@ -1948,7 +1996,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
     const unsigned long long tp0 = SPROF_NOW();
     (void)tp0;
     // an updated leaf is the deepest level's path child (a catch-up leaf is unchanged)
-    backupPath<NI>(v, s, s.pathLen, leafSt, haveLeaf);
+    backupPath<NI, EXPL>(v, s, s.pathLen, leafSt, haveLeaf);
     tPath = SPROF_NOW() - tp0;
     s.playouts++;
     needCommit = v.nodes()[s.rootIdx].visits >= (uint32_t)s.visitLimit;
@@ -1972,7 +2020,7 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   return true;
 }
 
-template <int NI, bool MATCH = false>
+template <int NI, bool MATCH = false, bool EXPL = false>
 __global__ void __launch_bounds__(64, NI <= 4 ? 4 : 3) kBackup(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp) {
   // (constant views: the call to rareLeaf does not count as a write to *dp or *Tp, so
   // their uniform reads after it stay scalar loads)
@@ -1983,7 +2031,7 @@ __global__ void __launch_bounds__(64, NI <= 4 ? 4 : 3) kBackup(const SearchDev* 
     return;
   __shared__ __attribute__((aligned(16))) float scratch[3 * MAX_P];
   __shared__ GameDev s;
-  backupBody<NI, MATCH>(d, T, g, s, false, scratch);
+  backupBody<NI, MATCH, EXPL>(d, T, g, s, false, scratch);
 }
 
 // Round r's backup and round r+1's selection of one game in one kernel (no commit between
@@ -1998,7 +2046,7 @@ __global__ void __launch_bounds__(64, NI <= 4 ? 4 : 3) kBackup(const SearchDev* 
 #ifndef KC_FUSED_OCC
 #define KC_FUSED_OCC 4
 #endif
-template <int NI>
+template <int NI, bool EXPL = false>
 __global__ void __launch_bounds__(64, NI <= 2 ? KC_FUSED_OCC : 2) kBackupSelect(const SearchDev* __restrict__ dp,
                                                                       const DTables* __restrict__ Tp) {
   const SearchDev& d = *uniformConst(dp);  // constant views: see kBackup
@@ -2009,9 +2057,9 @@ __global__ void __launch_bounds__(64, NI <= 2 ? KC_FUSED_OCC : 2) kBackupSelect(
   __shared__ __attribute__((aligned(16))) float scratch[3 * MAX_P];
   __shared__ uint32_t hasBits[(MAX_P + 31) / 32];
   __shared__ GameDev s;
-  const bool loaded = backupBody<NI>(d, T, g, s, true, scratch);
+  const bool loaded = backupBody<NI, false, EXPL>(d, T, g, s, true, scratch);
   // (the selection's root policy reuses the backup's scratch)
-  selectBody<NI>(d, T, g, s, loaded, true, hasBits, scratch);
+  selectBody<NI, false, EXPL>(d, T, g, s, loaded, true, hasBits, scratch);
 }
 
 #ifdef KC_SEARCH_PROFILE
@@ -2080,7 +2128,7 @@ KC_D void lcbAndRadius(const SP& sp, int pla, uint32_t cVisits, float cWs, float
 // oracle playSelectionValuesAt (getPlaySelectionValues searchresults.cpp:63-309) on node
 // ri with policy pol; the over-explored-children reduction and direct policy moves are
 // root-only.  posOut/vals are LDS arrays [P]; returns the count (uniform).
-template <int NI>
+template <int NI, bool EXPL = false>
 KC_D int playSelectionValuesAt(const GV& v, const SP& sp, const GameDev& s, int ri, const float* pol, bool isRoot,
                                float scaleMaxToAtLeast, bool allowDirect, int* posOut, float* vals, bool useLcb) {
   const Node& n = v.nodes()[ri];
@@ -2146,7 +2194,9 @@ KC_D int playSelectionValuesAt(const GV& v, const SP& sp, const GameDev& s, int 
   }
   if(isRoot && k > 0) {
     const float fpu = fpuValue(sp, n, pla, true, 1.0f);
-    const float scaling = exploreScaling(sp, total);
+    float scaling = exploreScaling(sp, total);
+    if constexpr(EXPL)
+      scaling = scaling * exploreStdevFactor(explOf(v), n.visits, n.weightSum, n.utilityAvg, n.utilitySqAvg);
     float bp = 0.0f, bu = 0.0f;
     uint32_t bvis = 0;
 #pragma unroll
@@ -2295,10 +2345,10 @@ KC_D int playSelectionValuesAt(const GV& v, const SP& sp, const GameDev& s, int 
 }
 
 // oracle playSelectionValues: the root with its noised policy.
-template <int NI>
+template <int NI, bool EXPL = false>
 KC_D int playSelectionValues(const GV& v, const SP& sp, const GameDev& s, float scaleMaxToAtLeast, bool allowDirect,
                              int* posOut, float* vals, bool useLcb) {
-  return playSelectionValuesAt<NI>(v, sp, s, s.rootIdx, v.rootNoised(), true, scaleMaxToAtLeast, allowDirect, posOut,
+  return playSelectionValuesAt<NI, EXPL>(v, sp, s, s.rootIdx, v.rootNoised(), true, scaleMaxToAtLeast, allowDirect, posOut,
                                    vals, useLcb);
 }
 
@@ -3137,14 +3187,14 @@ KC_D void emitSideRow(const GV& v, const GameDev& s, const TurnRec& rec, DRng& r
 // oracle searchTargets: extractPolicyTarget (play.cpp:635-672; scaleMaxToAtLeast 10, no
 // direct policy moves) into pt (global [P]) and getPolicySurpriseAndEntropy
 // (searchresults.cpp:486-550) at node ni with policy pol.
-template <int NI>
+template <int NI, bool EXPL = false>
 KC_D void searchTargets(const GV& v, const SP& sp, const GameDev& s, int ni, const float* pol, bool isRoot,
                         int16_t* pt, TurnRec& rec, int* posv, float* vals, float* tmp, float* tmp2) {
   const int P = v.d.P;
   for(int p = v.lane; p < P; p += 64)
     pt[p] = 0;
   {
-    int m = playSelectionValuesAt<NI>(v, sp, s, ni, pol, isRoot, 10.0f, false, posv, vals, sp.useLcb);
+    int m = playSelectionValuesAt<NI, EXPL>(v, sp, s, ni, pol, isRoot, 10.0f, false, posv, vals, sp.useLcb);
     float mx = 0.0f;
     for(int i = v.lane; i < m; i += 64)
       mx = vals[i] > mx ? vals[i] : mx;
@@ -3155,7 +3205,7 @@ KC_D void searchTargets(const GV& v, const SP& sp, const GameDev& s, int ni, con
       pt[posv[i]] = (int16_t)roundf(vals[i] * factor);
   }
   waveSync();
-  int m = playSelectionValuesAt<NI>(v, sp, s, ni, pol, isRoot, 1.0f, true, posv, vals, sp.useLcb);
+  int m = playSelectionValuesAt<NI, EXPL>(v, sp, s, ni, pol, isRoot, 1.0f, true, posv, vals, sp.useLcb);
   const float sumV = seqSum(vals, m, v.lane);
   // per-child terms (0 where the oracle skips), summed in order on lane 0
   waveSync();
@@ -3209,7 +3259,7 @@ KC_D void rawStats(const GV& v, float win, float loss, const float* pol, TurnRec
 // pre-order walk with an explicit stack: a side row at every non-root node reached
 // only through the best moves of the player to move there; excl0/excl1 skipped at the
 // root.  Frames and boards live in LDS; every lane walks the same path.
-template <int NI>
+template <int NI, bool EXPL = false>
 KC_D void recordTreePositions(const GV& v, const SP& sp, const GameDev& s, DRng& rng, int excl0, int excl1,
                               uint32_t rootVisits, int gameNumMeta, int* posv, float* vals, float* tmp, float* tmp2) {
   constexpr int MAXD = 5;
@@ -3236,7 +3286,7 @@ KC_D void recordTreePositions(const GV& v, const SP& sp, const GameDev& s, DRng&
       }
       if((fFlags[depth] & 1) && ni != s.rootIdx) {
         TurnRec rec;
-        searchTargets<NI>(v, sp, s, ni, v.pol(ni), false, pt, rec, posv, vals, tmp, tmp2);
+        searchTargets<NI, EXPL>(v, sp, s, ni, v.pol(ni), false, pt, rec, posv, vals, tmp, tmp2);
         const Node& n = v.nodes()[ni];
         rawStats(v, n.nnWin, n.nnLoss, v.pol(ni), rec, tmp);
         valueTargets(n, rec);
@@ -3652,7 +3702,7 @@ __global__ void __launch_bounds__(64 * ROWS_WAVES) kRows(const SearchDev* __rest
 // play.cpp:635-704, getPolicySurpriseAndEntropy searchresults.cpp:486-550, makeMove)
 // MATCH (two-network match play): the game record carries the candidate's colour and no
 // rows are emitted; the config admits no side positions, forks or tree positions there.
-template <int NI, bool MATCH = false>
+template <int NI, bool MATCH = false, bool EXPL = false>
 __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp) {
   const SearchDev& d = *dp;
   if((int)blockIdx.x >= *d.commitCount)
@@ -3693,7 +3743,7 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
   const bool side = s.sideMode != 0;
   // move choice: self-play disables LCB for the game's moves (runBotWithLimits
   // play.cpp:1040-1046), not for a side position's response (:1590)
-  int n = playSelectionValues<NI>(v, *v.sp, s, 0.0f, true, posv, vals, side ? sp.useLcb != 0 : false);
+  int n = playSelectionValues<NI, EXPL>(v, *v.sp, s, 0.0f, true, posv, vals, side ? sp.useLcb != 0 : false);
   if(n <= 0) {
     s.err = ERR_NO_CANDIDATE;
     n = 1;
@@ -3716,14 +3766,14 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
   int16_t* pt = side ? d.sidePol + (size_t)g * P : v.turnPol(t);
   waveSync();
   // the targets run after runBotWithLimits restored the base parameters (play.cpp:1066, :1307-1320)
-  searchTargets<NI>(v, sp, s, s.rootIdx, v.rootNoised(), true, pt, rec, posv, vals, tmp, tmp2);
+  searchTargets<NI, EXPL>(v, sp, s, s.rootIdx, v.rootNoised(), true, pt, rec, posv, vals, tmp, tmp2);
   rawStats(v, s.rawWin, s.rawLoss, v.rawPolicy(), rec, tmp);
   const bool recordTree = sp.recordTree != 0 && sp.recordTreeWeight > 0.0f;
   if(side) {
     emitSideRow(v, s, rec, rng, s.root, s.gameNum - 1);
     // its subtree positions (play.cpp:1612-1628)
     if(recordTree)
-      recordTreePositions<NI>(v, sp, s, rng, -1, -1, r.visits, s.gameNum - 1, posv, vals, tmp, tmp2);
+      recordTreePositions<NI, EXPL>(v, sp, s, rng, -1, -1, r.visits, s.gameNum - 1, posv, vals, tmp, tmp2);
     // occasionally continue: the response, then a forking move from the network's
     // policy there becomes another side position (play.cpp:1632-1656)
     if(rng.uni() < 0.25f) {
@@ -3759,7 +3809,7 @@ __global__ void __launch_bounds__(64) kCommit(const SearchDev* __restrict__ dp, 
   // (play.cpp:1347-1361)
   if(recordTree) {
     waveSync();
-    recordTreePositions<NI>(v, sp, s, rng, chosen, forkMove, r.visits, s.gameNum, posv, vals, tmp, tmp2);
+    recordTreePositions<NI, EXPL>(v, sp, s, rng, chosen, forkMove, r.visits, s.gameNum, posv, vals, tmp, tmp2);
   }
   rec.cell = (int8_t)(chosen % A);
   rec.dir = (int8_t)(chosen / A);
@@ -4225,6 +4275,46 @@ __global__ void kGameTreeSides(const SearchDev* __restrict__ dp, int g, int maxN
   gameTreeBody<true>(*dp, g, maxNodes, nodesOut, edgesOut, count);
 }
 
+// The priors beside kGameTree's export, in its breadth-first node order: priorsOut [maxNodes][P]
+// f32 bits, each node's child priors (Edge::prior) in slot order, and nextOut [maxNodes][2], its
+// cached next expansion (nextPrior bits, nextPos).  order [maxNodes]: scratch for the index map.
+__global__ void kGameTreePriors(const SearchDev* __restrict__ dp, int g, int maxNodes, uint32_t* priorsOut,
+                                uint32_t* nextOut, int32_t* order, int32_t* count) {
+  if(threadIdx.x != 0)
+    return;
+  const SearchDev& d = *dp;
+  const GameDev& s = d.games[g];
+  const Node* NS = d.nodes + (size_t)g * d.cap;
+  if(s.rootIdx < 0) {
+    *count = 0;
+    return;
+  }
+  int n = 1, head = 0;
+  order[0] = s.rootIdx;
+  while(head < n && head < maxNodes) {
+    const int idx = order[head];
+    const Node& x = NS[idx];
+    nextOut[2 * (size_t)head] = f2u(x.nextPrior);
+    nextOut[2 * (size_t)head + 1] = (uint32_t)x.nextPos;
+    const NodeEdges E{d.edges + ((size_t)g * d.cap + idx) * INLINE_EDGES,
+                      d.edgePool + ((size_t)g * 2 + s.edgeSel) * d.edgePoolCap + x.edgeBase};
+    for(int i = 0; i < x.numChildren; i++) {
+      const int c = (int)E[i].child;
+      int ci = -1;
+      for(int q = 0; q < n; q++)
+        if(order[q] == c) {
+          ci = q;
+          break;
+        }
+      if(ci < 0 && n < maxNodes)
+        order[n++] = c;
+      priorsOut[(size_t)head * d.P + i] = f2u(E[i].prior);
+    }
+    head++;
+  }
+  *count = n;
+}
+
 // ---------------------------------------------------------------------------
 // Position analysis (DESIGN.md "Analysis").  A slot holds one query or is idle.  An idle slot
 // stands in PH_COMMIT with no leaf and no commit-list entry: kSelect gives it no network row
@@ -4544,7 +4634,7 @@ __global__ void __launch_bounds__(64) kAnalysisLoad(const SearchDev* __restrict_
 // the principal variation: each lane walks its own children's lines, at every node to the
 // child with the most edge visits (ties: lower slot), until a node without children or a
 // terminal node.  The tree is not changed.
-template <int NI>
+template <int NI, bool EXPL = false>
 __global__ void __launch_bounds__(64) kAnalysisReport(const SearchDev* __restrict__ dp, const DTables* __restrict__ Tp) {
   // (constant views, as in kBackup: uniform reads stay scalar loads after the kernel's own stores)
   const SearchDev& d = *uniformConst(dp);
@@ -4566,7 +4656,7 @@ __global__ void __launch_bounds__(64) kAnalysisReport(const SearchDev* __restric
   const Node root = NS[s.rootIdx];
   const int k = root.numChildren, pla = root.nextPla;
   // (a root without children gets the direct policy moves here: not children, not reported)
-  playSelectionValues<NI>(v, sp, s, 0.0f, true, posv, vals, sp.useLcb != 0);
+  playSelectionValues<NI, EXPL>(v, sp, s, 0.0f, true, posv, vals, sp.useLcb != 0);
   const int ri = newResult(d, v.lane);
   const NodeEdges E = v.edges(s.rootIdx, root.edgeBase);
   const float* rp = v.pol(s.rootIdx);
@@ -4761,10 +4851,34 @@ static void launchEv(K kernel, dim3 grid, dim3 block, uint32_t lds, hipStream_t 
     hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
 }
 
+// Whether the engine's searches carry variance-scaled exploration or noise pruning (explore.h;
+// DESIGN.md 8g): the launchers then take the EXPL instantiations, every other engine the ones
+// without them, which hold no trace of either mechanism.
+static bool explLaunch(const SearchDev& d) { return explOn(d.ex) || explOn(d.ex1); }
+
+// KERNEL<NI, ...> by the engine's items per lane.
+#define KC_BY_ITEMS(LAUNCH, KERNEL, ...)                         \
+  switch(laneItems(d.P)) {                                       \
+    case 2: LAUNCH((KERNEL<2, __VA_ARGS__>)); break;             \
+    case 4: LAUNCH((KERNEL<4, __VA_ARGS__>)); break;             \
+    default: LAUNCH((KERNEL<7, __VA_ARGS__>)); break;            \
+  }
+
 void launchSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEvent_t e0, hipEvent_t e1,
                   bool resetCommit) {
   const DTables* T = d.T;
   const int rc = resetCommit ? 1 : 0;
+#define KC_L(K) launchEv(K, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc)
+  if(explLaunch(d)) {
+    if(d.matchMode) {
+      KC_BY_ITEMS(KC_L, kSelect, true, true)
+    } else {
+      KC_BY_ITEMS(KC_L, kSelect, false, true)
+    }
+    KC_HIP(hipGetLastError());
+    return;
+  }
+#undef KC_L
   if(d.matchMode) {
     switch(laneItems(d.P)) {
       case 2: launchEv(kSelect<2, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
@@ -4784,6 +4898,16 @@ void launchSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEv
 
 void launchBackup(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   const DTables* T = d.T;
+#define KC_L(K) launchEv(K, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T)
+  if(explLaunch(d)) {
+    if(d.matchMode) {
+      KC_BY_ITEMS(KC_L, kBackup, true, true)
+    } else {
+      KC_BY_ITEMS(KC_L, kBackup, false, true)
+    }
+    KC_HIP(hipGetLastError());
+    return;
+  }
   if(d.matchMode) {
     switch(laneItems(d.P)) {
       case 2: launchEv(kBackup<2, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
@@ -4803,6 +4927,12 @@ void launchBackup(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEv
 
 void launchBackupSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
   const DTables* T = d.T;
+  if(explLaunch(d)) {
+    KC_BY_ITEMS(KC_L, kBackupSelect, true)
+    KC_HIP(hipGetLastError());
+    return;
+  }
+#undef KC_L
   switch(laneItems(d.P)) {
     case 2: launchEv(kBackupSelect<2>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
     case 4: launchEv(kBackupSelect<4>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
@@ -4827,6 +4957,18 @@ void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
     // the idle slots take the queries submitted so far
     hipLaunchKernelGGL(kAnalysisSubmitted, dim3(1), dim3(1), 0, st, dd, d.aSubmitted);
     KC_HIP(hipGetLastError());
+    if(explLaunch(d)) {
+#define KC_L(K) hipLaunchKernelGGL(K, dim3(d.G), dim3(64), 0, st, dd, d.T)
+      KC_BY_ITEMS(KC_L, kAnalysisReport, true)
+      switch(laneItems(d.P)) {
+        case 2: KC_L(kAnalysisLoad<2>); break;
+        case 4: KC_L(kAnalysisLoad<4>); break;
+        default: KC_L(kAnalysisLoad<7>); break;
+      }
+#undef KC_L
+      KC_HIP(hipGetLastError());
+      return;
+    }
     switch(laneItems(d.P)) {
       case 2:
         hipLaunchKernelGGL(kAnalysisReport<2>, dim3(d.G), dim3(64), 0, st, dd, d.T);
@@ -4845,11 +4987,17 @@ void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
     return;
   }
   const size_t lds = commitLdsBytes(d.cap);
+  const bool expl = explLaunch(d);
+#define KC_L(K) hipLaunchKernelGGL(K, dim3(d.G), dim3(64), lds, st, dd, d.T)
   if(d.matchMode) {  // no kRows: match play writes no training rows
-    switch(laneItems(d.P)) {
-      case 2: hipLaunchKernelGGL((kCommit<2, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
-      case 4: hipLaunchKernelGGL((kCommit<4, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
-      default: hipLaunchKernelGGL((kCommit<7, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+    if(expl) {
+      KC_BY_ITEMS(KC_L, kCommit, true, true)
+    } else {
+      switch(laneItems(d.P)) {
+        case 2: hipLaunchKernelGGL((kCommit<2, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+        case 4: hipLaunchKernelGGL((kCommit<4, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+        default: hipLaunchKernelGGL((kCommit<7, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+      }
     }
     KC_HIP(hipGetLastError());
     if(d.spN > 0) {
@@ -4858,11 +5006,16 @@ void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
     }
     return;
   }
-  switch(laneItems(d.P)) {
-    case 2: hipLaunchKernelGGL(kCommit<2>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;
-    case 4: hipLaunchKernelGGL(kCommit<4>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;
-    default: hipLaunchKernelGGL(kCommit<7>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+  if(expl) {
+    KC_BY_ITEMS(KC_L, kCommit, false, true)
+  } else {
+    switch(laneItems(d.P)) {
+      case 2: hipLaunchKernelGGL(kCommit<2>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+      case 4: hipLaunchKernelGGL(kCommit<4>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+      default: hipLaunchKernelGGL(kCommit<7>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;
+    }
   }
+#undef KC_L
   KC_HIP(hipGetLastError());
   hipLaunchKernelGGL(kRows, dim3(d.G), dim3(64 * ROWS_WAVES), 0, st, dd, d.T);
   KC_HIP(hipGetLastError());
@@ -4877,6 +5030,12 @@ void launchGameTree(const SearchDev* dd, int slot, int maxNodes, uint32_t* nodes
   hipLaunchKernelGGL(kGameTree, dim3(1), dim3(64), 0, st, dd, slot, maxNodes, nodesOut, edgesOut, count);
   KC_HIP(hipGetLastError());
   hipLaunchKernelGGL(kGameTreeSides, dim3(1), dim3(64), 0, st, dd, slot, maxNodes, nodesOut, edgesOut, count);
+  KC_HIP(hipGetLastError());
+}
+
+void launchGameTreePriors(const SearchDev* dd, int slot, int maxNodes, uint32_t* priorsOut, uint32_t* nextOut,
+                          int32_t* order, int32_t* count, hipStream_t st) {
+  hipLaunchKernelGGL(kGameTreePriors, dim3(1), dim3(64), 0, st, dd, slot, maxNodes, priorsOut, nextOut, order, count);
   KC_HIP(hipGetLastError());
 }
 

@@ -5,6 +5,7 @@
 #include "selfplay.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <cstring>
 
 namespace kc {
@@ -112,6 +113,27 @@ Unc toUnc(const coffee_uncertainty_params& p) {
   if(!in(p.uncertainty_max_weight, 1.0f, 100.0f))
     throw std::invalid_argument("uncertainty_max_weight must be in [1, 100]");
   return Unc{p.use_uncertainty, p.uncertainty_coeff, p.uncertainty_exponent, p.uncertainty_max_weight};
+}
+
+Expl toExpl(const coffee_exploration_params& p) {
+  // !(a <= x && x <= b) also rejects NaN; the upper bounds reject +inf
+  auto in = [](float x, float lo, float hi) { return x >= lo && x <= hi; };
+  if(p.use_noise_pruning != 0 && p.use_noise_pruning != 1)
+    throw std::invalid_argument("use_noise_pruning must be 0 or 1");
+  if(!in(p.noise_prune_utility_scale, 0.001f, 10.0f))
+    throw std::invalid_argument("noise_prune_utility_scale must be in [0.001, 10]");
+  if(!in(p.noise_pruning_cap, 0.0f, FLT_MAX))
+    throw std::invalid_argument("noise_pruning_cap must be finite and >= 0");
+  if(!in(p.cpuct_utility_stdev_prior, 0.0f, 10.0f))
+    throw std::invalid_argument("cpuct_utility_stdev_prior must be in [0, 10]");
+  if(!in(p.cpuct_utility_stdev_prior_weight, 0.0f, 100.0f))
+    throw std::invalid_argument("cpuct_utility_stdev_prior_weight must be in [0, 100]");
+  if(!in(p.cpuct_utility_stdev_scale, 0.0f, 1.0f))
+    throw std::invalid_argument("cpuct_utility_stdev_scale must be in [0, 1]");
+  if(p.cpuct_utility_stdev_prior == 0.0f && p.cpuct_utility_stdev_scale > 0.0f)
+    throw std::invalid_argument("cpuct_utility_stdev_prior must be > 0 with cpuct_utility_stdev_scale > 0");
+  return Expl{p.use_noise_pruning,          p.noise_prune_utility_scale,        p.noise_pruning_cap,
+              p.cpuct_utility_stdev_prior, p.cpuct_utility_stdev_prior_weight, p.cpuct_utility_stdev_scale};
 }
 
 void validateMatchConfig(const coffee_match_config& c) {
@@ -493,6 +515,10 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* cons
     coffee_uncertainty_params_default(&u);
     d.unc = toUnc(u);  // off
     d.unc1 = d.unc;
+    coffee_exploration_params e;
+    coffee_exploration_params_default(&e);
+    d.ex = toExpl(e);  // off
+    d.ex1 = d.ex;
   }
   d.sp1 = d.sp;
   if(perSide) {
@@ -679,6 +705,24 @@ void SelfplayEngine::setUncertainty(const coffee_uncertainty_params& p) {
   hd_.unc = u;
   // nothing runs yet (the constructor synchronised its initialisation): a plain copy
   KC_HIP(hipMemcpy(&dd_->unc, &hd_.unc, sizeof(Unc), hipMemcpyHostToDevice));
+}
+
+void SelfplayEngine::setExploration(int side, const coffee_exploration_params& p) {
+  const Expl e = toExpl(p);
+  if(hd_.matchPerSide ? (side != 0 && side != 1) : side != -1)
+    throw std::invalid_argument(hd_.matchPerSide ? "set_exploration: side must be 0 or 1 on an engine with per-side settings"
+                                                 : "set_exploration: side must be -1 on an engine without per-side settings");
+  // like set_uncertainty: a tree must never mix the two rules
+  if(rounds_ > 0 || aSubmitted_ > 0)
+    throw std::invalid_argument(hd_.analysisMode ? "set_exploration: only before the first query and round"
+                                                 : "set_exploration: only before the engine's first round");
+  if(side != 1)
+    hd_.ex = e;
+  if(side != 0)
+    hd_.ex1 = e;
+  // nothing runs yet (the constructor synchronised its initialisation): plain copies
+  KC_HIP(hipMemcpy(&dd_->ex, &hd_.ex, sizeof(Expl), hipMemcpyHostToDevice));
+  KC_HIP(hipMemcpy(&dd_->ex1, &hd_.ex1, sizeof(Expl), hipMemcpyHostToDevice));
 }
 
 void SelfplayEngine::setRootOptions(const coffee_analysis_root_options& o) {
@@ -1286,6 +1330,48 @@ int SelfplayEngine::gameTree(int slot, int maxNodes, uint32_t* nodes, uint32_t* 
     KC_HIP(hipMemcpy(edges, de, (size_t)maxNodes * hd_.P * 3 * 4, hipMemcpyDeviceToHost));
   for(void* p : tmp)
     (void)hipFree(p);
+  return n;
+}
+
+int SelfplayEngine::gameTreePriors(int slot, int maxNodes, float* priors, float* nextPrior, int32_t* nextPos) {
+  if(slot < 0 || slot >= hd_.G || maxNodes <= 0)
+    throw std::invalid_argument("slot/max_nodes out of range");
+  // (weak in search.h: a host-only link of the engine has no kernels; never null in the library)
+  if(!launchGameTreePriors)
+    throw InternalError("game_tree_priors: this build has no export kernel");
+  sync();
+  std::vector<void*> tmp;
+  struct Guard {
+    std::vector<void*>& t;
+    ~Guard() {
+      for(void* p : t)
+        (void)hipFree(p);
+    }
+  } guard{tmp};
+  const size_t np = (size_t)maxNodes * hd_.P;
+  uint32_t* dp = devAlloc<uint32_t>(tmp, np, false);
+  uint32_t* dn = devAlloc<uint32_t>(tmp, (size_t)maxNodes * 2, false);
+  int32_t* dorder = devAlloc<int32_t>(tmp, (size_t)maxNodes, false);
+  int32_t* dc = devAlloc<int32_t>(tmp, 1, false);
+  KC_HIP(hipMemsetAsync(dp, 0, np * 4, stream_));
+  KC_HIP(hipMemsetAsync(dn, 0, (size_t)maxNodes * 2 * 4, stream_));
+  KC_HIP(hipMemsetAsync(dc, 0, 4, stream_));
+  launchGameTreePriors(dd_, slot, maxNodes, dp, dn, dorder, dc, stream_);
+  KC_HIP(hipStreamSynchronize(stream_));
+  int n = 0;
+  KC_HIP(hipMemcpy(&n, dc, 4, hipMemcpyDeviceToHost));
+  if(priors)
+    KC_HIP(hipMemcpy(priors, dp, np * 4, hipMemcpyDeviceToHost));
+  if(nextPrior || nextPos) {
+    std::vector<uint32_t> nx((size_t)maxNodes * 2);
+    KC_HIP(hipMemcpy(nx.data(), dn, nx.size() * 4, hipMemcpyDeviceToHost));
+    for(int i = 0; i < maxNodes; i++) {
+      if(nextPrior)
+        memcpy(&nextPrior[i], &nx[2 * (size_t)i], 4);
+      if(nextPos)
+        nextPos[i] = (int32_t)nx[2 * (size_t)i + 1];
+    }
+  }
   return n;
 }
 

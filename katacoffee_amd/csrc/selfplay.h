@@ -15,6 +15,10 @@ SP toSP(const coffee_search_params& p);
 // Checks the ranges (throws std::invalid_argument naming the setting; NaN is out of range)
 // and converts.
 Unc toUnc(const coffee_uncertainty_params& p);
+// The device block of coffee_exploration_params; throws std::invalid_argument outside the
+// reference's ranges (setup.cpp:453-470, :520-537), for a non-finite value and for prior 0 with
+// scale > 0.
+Expl toExpl(const coffee_exploration_params& p);
 // Start positions: the parameters' ranges; the thresholds of a table on the host (startpos.h);
 // the check kernel on a host table at a geometry.  Each throws std::invalid_argument naming
 // the setting or the first bad sample.
@@ -58,6 +62,8 @@ class SelfplayEngine {
   // first round (analysis: and the first query); throws std::invalid_argument afterwards or
   // for out-of-range values, without touching the device.
   void setUncertainty(const coffee_uncertainty_params& p);
+  // side: -1 on an engine without per-side settings, 0 / 1 on one with them
+  void setExploration(int side, const coffee_exploration_params& p);
   // Start positions: checks the parameters and every sample (kStartPosCheck),
   // builds the thresholds and uploads both once the engine stream is idle; between steps at any time.
   // Throws std::invalid_argument (naming the first bad sample) with the engine untouched.
@@ -90,6 +96,7 @@ class SelfplayEngine {
   void setModelBytes(const void* data, size_t bytes);
   void gameInfo(int slot, int64_t* info);
   int gameTree(int slot, int maxNodes, uint32_t* nodes, uint32_t* edges);
+  int gameTreePriors(int slot, int maxNodes, float* priors, float* nextPrior, int32_t* nextPos);
   void rootPolicy(int slot, float* out);
   // every = 0: off; N: time every N-th launch of each kernel group (HIP events;
   // each event pair costs a few microseconds of stream gap, so sampling keeps

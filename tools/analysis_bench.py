@@ -69,6 +69,9 @@ def main():
     ap.add_argument("--cache-log2", type=int, default=21)
     ap.add_argument("--uncertainty", action="store_true",
                     help="uncertainty weighting on (set_uncertainty(use_uncertainty=1), default values) in both engines")
+    ap.add_argument("--exploration", action="store_true",
+                    help="the reference's match / analysis exploration: cpuctUtilityStdevScale 0.85 and noise pruning "
+                         "(set_exploration) in both engines")
     ap.add_argument("--root-symmetry-pruning", action="store_true",
                     help="root symmetry pruning on in the analysis engine")
     a = ap.parse_args()
@@ -81,6 +84,8 @@ def main():
         an = kc.Analysis(X, Y, W, num_slots=a.slots, model_path=path, search=search, query_capacity=4 * a.slots,
                          **common)
         an.set_uncertainty(use_uncertainty=int(a.uncertainty))
+        if a.exploration:
+            an.set_exploration(**dict(cpuct_utility_stdev_scale=0.85, use_noise_pruning=1))
         has_root = hasattr(kc.lib(), "coffee_root_mask")  # (absent in earlier builds run as A/B references)
         if a.root_symmetry_pruning:
             an.set_root_options(root_symmetry_pruning=True)
@@ -130,6 +135,8 @@ def main():
         sp = kc.Selfplay(X, Y, W, num_games=a.slots, model_path=path, max_visits=a.visits, start_stagger=a.visits,
                          **common, **over)
         sp.set_uncertainty(use_uncertainty=int(a.uncertainty))
+        if a.exploration:
+            sp.set_exploration(**dict(cpuct_utility_stdev_scale=0.85, use_noise_pruning=1))
         sp.step(a.warmup)
         sp.sync()
         sp.drain_rows()

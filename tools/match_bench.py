@@ -57,6 +57,9 @@ def main():
     ap.add_argument("--cache-log2", type=int, default=21)
     ap.add_argument("--uncertainty", action="store_true",
                     help="uncertainty weighting on (set_uncertainty(use_uncertainty=1), default values) in both engines")
+    ap.add_argument("--exploration", action="store_true",
+                    help="the reference's match / analysis exploration: cpuctUtilityStdevScale 0.85 and noise pruning "
+                         "(set_exploration) in both engines")
     ap.add_argument("--equal-sides", action="store_true",
                     help="per-side settings with both sides the engine's own parameters (kc.Match(sides=...))")
     ap.add_argument("--share-net", action="store_true",
@@ -81,11 +84,16 @@ def main():
                      **common, **extra)
         if not a.equal_sides:  # (the sides carry their own)
             m.set_uncertainty(use_uncertainty=int(a.uncertainty))
+        if a.exploration:
+            for side in ((0, 1) if a.equal_sides else (-1,)):
+                m.set_exploration(side=side, **dict(cpuct_utility_stdev_scale=0.85, use_noise_pruning=1))
         msecs, mgames, mst = timed(m, a.rounds, a.warmup, a.repeats, m.drain_games)
         m.close()
         over.pop("max_visits")
         s = kc.Selfplay(X, Y, W, model_path=paths[0], max_visits=a.visits, **common, **over)
         s.set_uncertainty(use_uncertainty=int(a.uncertainty))
+        if a.exploration:
+            s.set_exploration(**dict(cpuct_utility_stdev_scale=0.85, use_noise_pruning=1))
 
         def drain_sp():
             s.drain_rows()
