@@ -686,6 +686,47 @@ int coffee_match_game_tree_priors(coffee_match* h, int slot, int max_nodes, floa
 int coffee_analysis_game_tree_priors(coffee_analysis* h, int slot, int max_nodes, float* priors, float* next_prior,
                                      int32_t* next_pos, int* n_nodes);
 
+/* ---- wide root noise and futile-visit pruning (the reference's wideRootNoise, on
+ *      at 0.04 in its analysis set-up, and futileVisitsThreshold) ----
+ * Both act in the root's child selection only, during search only; play-selection values, move
+ * choice, LCB, policy targets and the analysis report are untouched.
+ * Futile-visit pruning (getExploreSelectionValueOfChild, searchexplorehelpers.cpp:136-147,
+ * :193-201), checked before the rootDesiredPerChildVisits funnel: with max_w the largest child
+ * weight, wpv = root weight_sum / visits and left = visit limit - root visits,
+ *   child:     need = (thr * max_w) * ((edge_visits + 1) / (w + wpv)); futile if child_visits + left < need
+ *   new move:  need = (thr * max_w) * (1 / wpv);                       futile if left < need
+ * A futile move's selection value is -FLT_MAX (an illegal or masked move's stays -inf).
+ * Wide root noise (maybeApplyWideRootNoise, :71-87), on every legal child the funnel did not take
+ * and on the best unexpanded move: the prior becomes prior^(1 / (4 wide + 1)) and with probability
+ * 1/2 the utility from the mover's side gains wide * |gauss|.  The draws do not come from the
+ * game's stream: they are a function of the game's stream seed, the root's turn, the root's
+ * visits at the selection and the move's policy position alone.
+ * Off (both 0, the default of all three engines), nothing changes. */
+typedef struct coffee_root_search_params {
+  float wide_root_noise;         /* 0, range [0, 5] */
+  float futile_visits_threshold; /* 0, allowed: 0 or [0.01, 1] */
+} coffee_root_search_params;
+void coffee_root_search_params_default(coffee_root_search_params* p);
+/* The two rules on the host (no device is touched), bit for bit what the search kernels compute.
+ * COFFEE_EINVAL for out-of-range or non-finite parameters.
+ * _wide_root_noise: the smoothed prior and the bonus of the move at policy position pos in the
+ * root selection at root_visits visits of turn `turn` of game game_num of global slot
+ * global_slot_or_stream (analysis: the query's stream and game number), on an engine created with
+ * `seed`.  With wide_root_noise 0: the prior unchanged and bonus 0.  Either output may be NULL.
+ * _futile_visits: *futile = 1 if the move is futile (is_new: the unexpanded candidate, whose edge /
+ * child arguments are ignored), else 0; always 0 with futile_visits_threshold 0. */
+int coffee_wide_root_noise(const coffee_root_search_params* p, uint64_t seed, uint32_t global_slot_or_stream,
+                           uint32_t game_num, int32_t turn, uint32_t root_visits, int32_t pos, float prior,
+                           float* smoothed_prior, float* bonus);
+int coffee_futile_visits(const coffee_root_search_params* p, float max_child_weight, float parent_weight_sum,
+                         int64_t parent_visits, int64_t visits_left, int64_t edge_visits, int64_t child_visits,
+                         float child_weight, int is_new, int* futile);
+/* Sets both rules of an engine, under coffee_*_set_exploration's rules (only before the first
+ * round / query; side -1 / 0 / 1 as there). */
+int coffee_selfplay_set_root_search(coffee_selfplay* h, const coffee_root_search_params* p);
+int coffee_analysis_set_root_search(coffee_analysis* h, const coffee_root_search_params* p);
+int coffee_match_set_root_search(coffee_match* h, int side, const coffee_root_search_params* p);
+
 /* ---- per-side match settings (the reference's `katago match`, whose search keys
  *      take a bot suffix, cpp/command/match.cpp) ----
  * A match engine whose two sides search with their own parameters and uncertainty weighting,

@@ -136,6 +136,11 @@ class ExplorationParams(ctypes.Structure):
                 ("cpuct_utility_stdev_prior_weight", ctypes.c_float), ("cpuct_utility_stdev_scale", ctypes.c_float)]
 
 
+class RootSearchParams(ctypes.Structure):
+    """coffee_root_search_params: wide root noise and futile-visit pruning."""
+    _fields_ = [("wide_root_noise", ctypes.c_float), ("futile_visits_threshold", ctypes.c_float)]
+
+
 class MatchSide(ctypes.Structure):
     """coffee_match_side: one side's search parameters and uncertainty weighting."""
     _fields_ = [("search", SearchParams), ("unc", UncertaintyParams)]
@@ -243,6 +248,8 @@ EXPORTS = [
     "coffee_exploration_params_default", "coffee_explore_stdev_factor", "coffee_prune_noise_weight",
     "coffee_selfplay_set_exploration", "coffee_analysis_set_exploration", "coffee_match_set_exploration",
     "coffee_selfplay_game_tree_priors", "coffee_match_game_tree_priors", "coffee_analysis_game_tree_priors",
+    "coffee_root_search_params_default", "coffee_wide_root_noise", "coffee_futile_visits",
+    "coffee_selfplay_set_root_search", "coffee_analysis_set_root_search", "coffee_match_set_root_search",
 ]
 
 
@@ -374,6 +381,16 @@ def lib():
             for f in (L.coffee_selfplay_game_tree_priors, L.coffee_match_game_tree_priors,
                       L.coffee_analysis_game_tree_priors):
                 f.argtypes = [c_p, c_i, c_i, c_p, c_p, c_p, c_p]
+        if hasattr(L, "coffee_wide_root_noise"):  # (absent in earlier builds run as A/B references)
+            L.coffee_root_search_params_default.argtypes = [c_p]
+            L.coffee_root_search_params_default.restype = None
+            L.coffee_wide_root_noise.argtypes = [c_p, c_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32,
+                                                 ctypes.c_uint32, ctypes.c_int32, ctypes.c_float, c_p, c_p]
+            L.coffee_futile_visits.argtypes = [c_p, ctypes.c_float, ctypes.c_float, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_float, c_i, c_p]
+            L.coffee_selfplay_set_root_search.argtypes = [c_p, c_p]
+            L.coffee_analysis_set_root_search.argtypes = [c_p, c_p]
+            L.coffee_match_set_root_search.argtypes = [c_p, c_i, c_p]
         _lib = L
     return _lib
 
@@ -488,6 +505,51 @@ def prune_noise_weight(weight, utility, prior, params=None, **over):
     check(lib().coffee_prune_noise_weight(ctypes.byref(p), len(w), _ptr(w), _ptr(u), _ptr(pr), _ptr(out),
                                           ctypes.byref(tot)))
     return out, np.float32(tot.value)
+
+
+def default_root_search_params(**over):
+    """coffee_root_search_params_default: both rules off (wide_root_noise 0,
+    futile_visits_threshold 0).  The reference's analysis set-up runs with wide_root_noise=0.04."""
+    p = RootSearchParams()
+    lib().coffee_root_search_params_default(ctypes.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def _root_search_params(params, over):
+    p = default_root_search_params() if params is None else RootSearchParams.from_buffer_copy(params)
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def wide_root_noise(seed, global_slot_or_stream, game_num, turn, root_visits, pos, prior, params=None, **over):
+    """(smoothed_prior, bonus) as np.float32 of the move at policy position `pos` in the root
+    selection at `root_visits` visits of turn `turn` of game `game_num` of global slot (analysis:
+    stream) `global_slot_or_stream` on an engine created with `seed`: coffee_wide_root_noise, the
+    host run of the search kernels' own sequence.  params: a RootSearchParams (default:
+    default_root_search_params()); keyword overrides on top."""
+    p = _root_search_params(params, over)
+    sm, b = ctypes.c_float(), ctypes.c_float()
+    check(lib().coffee_wide_root_noise(ctypes.byref(p), int(seed), int(global_slot_or_stream), int(game_num),
+                                       int(turn), int(root_visits), int(pos), ctypes.c_float(float(prior)),
+                                       ctypes.byref(sm), ctypes.byref(b)))
+    return np.float32(sm.value), np.float32(b.value)
+
+
+def futile_visits(max_child_weight, parent_weight_sum, parent_visits, visits_left, edge_visits=0, child_visits=0,
+                  child_weight=0.0, is_new=False, params=None, **over):
+    """Whether futile-visit pruning skips a root move (coffee_futile_visits, the host run of the
+    search kernels' own sequence): an existing child by its edge visits, visits and weight, or with
+    is_new the unexpanded candidate.  params / overrides as wide_root_noise."""
+    p = _root_search_params(params, over)
+    out = ctypes.c_int()
+    check(lib().coffee_futile_visits(ctypes.byref(p), ctypes.c_float(float(max_child_weight)),
+                                     ctypes.c_float(float(parent_weight_sum)), int(parent_visits), int(visits_left),
+                                     int(edge_visits), int(child_visits), ctypes.c_float(float(child_weight)),
+                                     1 if is_new else 0, ctypes.byref(out)))
+    return bool(out.value)
 
 
 def _game_tree_priors(fn, h, P, slot, max_nodes):
@@ -981,6 +1043,13 @@ class Selfplay:
         p = _exploration_params(params, over)
         check(lib().coffee_selfplay_set_exploration(self.h, ctypes.byref(p)))
 
+    def set_root_search(self, params=None, **over):
+        """Wide root noise and futile-visit pruning (coffee_selfplay_set_root_search): a
+        RootSearchParams and / or its fields as keywords, e.g. wide_root_noise=0.04,
+        futile_visits_threshold=0.15.  Only before the engine's first round."""
+        p = _root_search_params(params, over)
+        check(lib().coffee_selfplay_set_root_search(self.h, ctypes.byref(p)))
+
     def set_start_positions(self, positions, prob, turn_weight_lambda=0.0, start_policy_init_area_prop=0.0):
         """Start positions (coffee_selfplay_set_start_positions): games that start from now on
         begin with probability `prob` from a sample of `positions` (see start_positions()),
@@ -1132,8 +1201,8 @@ class Match:
     search: a SearchParams to start from instead of default_match_params(); keyword
     overrides apply on top of either.
     sides (coffee_match_create2): a pair, side 0 (the baseline's side) then side 1 (the
-    candidate's), each a dict of SearchParams / UncertaintyParams field overrides on top of
-    the engine's search (uncertainty off), or a (SearchParams, UncertaintyParams) pair.  Every
+    candidate's), each a dict of SearchParams / UncertaintyParams / RootSearchParams field
+    overrides on top of the engine's search (uncertainty and root search off), or a (SearchParams, UncertaintyParams) pair.  Every
     search then runs with the parameters of the side that searches; set_uncertainty is
     refused.  The game-level settings (init_games_with_policy and its two area settings) stay
     the engine's.
@@ -1172,14 +1241,30 @@ class Match:
             return
         opts = MatchOptions()
         opts.share_net = 1 if share_net else 0
+        root_search = []
         if sides is not None:
             if not isinstance(sides, (tuple, list)) or len(sides) != 2:
                 raise CoffeeError("Match sides: a pair (side 0, side 1)")
             opts.per_side = 1
+            rfields = {n for n, _ in RootSearchParams._fields_}
             for i in range(2):
-                opts.side[i] = _match_side(search, sides[i], i)
+                spec = sides[i]
+                if isinstance(spec, dict):
+                    # (the root-search fields travel in their own struct: set after the create)
+                    root_search.append({k: v for k, v in spec.items() if k in rfields})
+                    spec = {k: v for k, v in spec.items() if k not in rfields}
+                else:
+                    root_search.append({})
+                opts.side[i] = _match_side(search, spec, i)
         self.opts = opts
         check(lib().coffee_match_create2(ctypes.byref(cfg), ctypes.byref(opts), ctypes.byref(self.h)))
+        for i, over in enumerate(root_search):
+            if over:
+                try:
+                    self.set_root_search(side=i, **over)
+                except CoffeeError:
+                    self.close()
+                    raise
 
     def step(self, rounds, stream=None):
         check(lib().coffee_match_step(self.h, rounds, stream))
@@ -1197,6 +1282,13 @@ class Match:
         settings, 0 / 1 on one with them.  Only before the engine's first round."""
         p = _exploration_params(params, over)
         check(lib().coffee_match_set_exploration(self.h, int(side), ctypes.byref(p)))
+
+    def set_root_search(self, params=None, side=-1, **over):
+        """Wide root noise and futile-visit pruning (coffee_match_set_root_search): a
+        RootSearchParams and / or its fields as keywords.  side: -1 on an engine without per-side
+        settings, 0 / 1 on one with them.  Only before the engine's first round."""
+        p = _root_search_params(params, over)
+        check(lib().coffee_match_set_root_search(self.h, int(side), ctypes.byref(p)))
 
     def set_start_positions(self, positions, prob, turn_weight_lambda=0.0, start_policy_init_area_prop=0.0):
         """Start positions (coffee_match_set_start_positions), as Selfplay.set_start_positions:
@@ -1362,6 +1454,13 @@ class Analysis:
         cpuct_utility_stdev_scale=0.85.  Only before the engine's first round and query."""
         p = _exploration_params(params, over)
         check(lib().coffee_analysis_set_exploration(self.h, ctypes.byref(p)))
+
+    def set_root_search(self, params=None, **over):
+        """Wide root noise and futile-visit pruning (coffee_analysis_set_root_search): a
+        RootSearchParams and / or its fields as keywords, e.g. wide_root_noise=0.04.  Only before
+        the engine's first round and query."""
+        p = _root_search_params(params, over)
+        check(lib().coffee_analysis_set_root_search(self.h, ctypes.byref(p)))
 
     def sync(self):
         check(lib().coffee_analysis_sync(self.h))

@@ -987,6 +987,75 @@ int coffee_analysis_game_tree_priors(coffee_analysis* h, int slot, int max_nodes
   });
 }
 
+// ---- wide root noise and futile-visit pruning (rootsearch.h: the sequences the kernels run) ----
+
+void coffee_root_search_params_default(coffee_root_search_params* p) {
+  if(!p)
+    return;
+  p->wide_root_noise = 0.0f;  // searchparams.cpp: both off
+  p->futile_visits_threshold = 0.0f;
+}
+
+int coffee_wide_root_noise(const coffee_root_search_params* p, uint64_t seed, uint32_t global_slot_or_stream,
+                           uint32_t game_num, int32_t turn, uint32_t root_visits, int32_t pos, float prior,
+                           float* smoothed_prior, float* bonus) {
+  return guarded([&] {
+    need(p != nullptr, "NULL argument");
+    need(turn >= 0 && pos >= 0 && pos < MAX_P, "turn or pos out of range");
+    const RootSearch r = toRootSearch(*p);
+    float sm = prior, b = 0.0f;
+    if(r.wide > 0.0f) {
+      const uint64_t key = wideRootKey(gameStreamSeed(seed, global_slot_or_stream, game_num), turn, root_visits);
+      b = wideBonus(r.wide, key, pos);
+      sm = wideSmoothedPrior(r.wide, prior);
+    }
+    if(smoothed_prior)
+      *smoothed_prior = sm;
+    if(bonus)
+      *bonus = b;
+  });
+}
+
+int coffee_futile_visits(const coffee_root_search_params* p, float max_child_weight, float parent_weight_sum,
+                         int64_t parent_visits, int64_t visits_left, int64_t edge_visits, int64_t child_visits,
+                         float child_weight, int is_new, int* futile) {
+  return guarded([&] {
+    need(p && futile, "NULL argument");
+    auto u32 = [](int64_t x) { return x <= 0 ? 0u : (x > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)x); };
+    need(visits_left >= INT32_MIN && visits_left <= INT32_MAX, "visits_left out of range");
+    const RootSearch r = toRootSearch(*p);
+    *futile = 0;
+    if(!(r.thr > 0.0f))
+      return;
+    // the kernels' own conversions: u32 visits, the visits left an i32 difference
+    const float wpv = parent_weight_sum / (float)u32(parent_visits);
+    const float left = (float)(int32_t)visits_left;
+    *futile = is_new ? futileNew(r.thr, max_child_weight, wpv, left)
+                     : futileChild(r.thr, max_child_weight, wpv, left, u32(edge_visits), u32(child_visits), child_weight);
+  });
+}
+
+int coffee_selfplay_set_root_search(coffee_selfplay* h, const coffee_root_search_params* p) {
+  return guarded([&] {
+    need(h && h->eng && p, "NULL argument");
+    h->eng->setRootSearch(-1, *p);
+  });
+}
+
+int coffee_analysis_set_root_search(coffee_analysis* h, const coffee_root_search_params* p) {
+  return guarded([&] {
+    need(h && h->eng && p, "NULL argument");
+    h->eng->setRootSearch(-1, *p);
+  });
+}
+
+int coffee_match_set_root_search(coffee_match* h, int side, const coffee_root_search_params* p) {
+  return guarded([&] {
+    need(h && h->eng && p, "NULL argument");
+    h->eng->setRootSearch(side, *p);
+  });
+}
+
 // ---- start positions (startpos.h: the thresholds and the pick the kernels run) ----
 
 void coffee_start_positions_params_default(coffee_start_positions_params* p) {

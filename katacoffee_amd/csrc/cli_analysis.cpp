@@ -330,6 +330,7 @@ int analysisMain(int argc, char** argv) {
   must(coffee_analysis_create(&c, &sv.h), "create analysis engine");
   must(coffee_analysis_set_uncertainty(sv.h, &s.unc), "set uncertainty");
   must(coffee_analysis_set_exploration(sv.h, &s.ex), "set exploration");
+  must(coffee_analysis_set_root_search(sv.h, &s.rs), "set root search");
   // the policy travels with every result: a query's includePolicy prints it, and the symmetry
   // copies read the legal moves off it
   const coffee_analysis_root_options ro{s.rootSymmetryPruning, 1};

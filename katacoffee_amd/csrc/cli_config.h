@@ -67,6 +67,9 @@ struct Settings {
   // (coffee_exploration_params_default: both off) unless the config turns them on, for all four
   // commands (the reference's loader defaults them on for analysis, GTP and match, setup.cpp:453-537)
   coffee_exploration_params ex = {0, 0.15f, FLT_MAX, 0.40f, 2.0f, 0.0f};
+  // wideRootNoise, futileVisitsThreshold: off unless the config sets them, for all
+  // four commands (the reference's loader defaults wideRootNoise to 0.04 for analysis, setup.cpp:725-730)
+  coffee_root_search_params rs = {0.0f, 0.0f};
   // rootSymmetryPruning (`katago analysis` only): off unless the config turns it on -- the
   // reference's loader defaults it on for analysis and GTP (setup.cpp:639-644)
   int32_t rootSymmetryPruning = 0;
@@ -249,6 +252,13 @@ inline void applyExplorationConfig(const ConfigReader& r, coffee_exploration_par
                                 ": must be > 0 with cpuctUtilityStdevScale > 0");
 }
 
+// The two root-search keys onto rs, with the reference's ranges (setup.cpp:725-730, :843-848;
+// r.suffix: the bot of `katago match`).
+inline void applyRootSearchConfig(const ConfigReader& r, coffee_root_search_params& rs) {
+  r.getfIn("wideRootNoise", rs.wide_root_noise, 0.0f, 5.0f);
+  r.getfIn("futileVisitsThreshold", rs.futile_visits_threshold, 0.01f, 1.0f);
+}
+
 inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& s) {
   const ConfigReader r{kv, ""};
   auto it = kv.find("bSizes");
@@ -282,6 +292,7 @@ inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& 
   }
   applySearchConfig(r, s.sp, s.unc);
   applyExplorationConfig(r, s.ex);
+  applyRootSearchConfig(r, s.rs);
   r.getb("rootSymmetryPruning", s.rootSymmetryPruning);
   // start positions (play.cpp:186-196 getters: the same ranges)
   r.gets("startPosesFromSgfDir", s.startPos.sgfDirs);
@@ -301,6 +312,7 @@ struct MatchBot {
   coffee_search_params sp;
   coffee_uncertainty_params unc;
   coffee_exploration_params ex;  // the six exploration keys, per bot like every search key
+  coffee_root_search_params rs;  // wideRootNoise / futileVisitsThreshold, likewise (off unless set)
 };
 
 inline void applyMatchBots(const std::map<std::string, std::string>& kv, const coffee_search_params& defSp,
@@ -319,6 +331,8 @@ inline void applyMatchBots(const std::map<std::string, std::string>& kv, const c
     applySearchConfig(r, bots[i].sp, bots[i].unc);
     bots[i].ex = defEx;
     applyExplorationConfig(r, bots[i].ex);
+    bots[i].rs = coffee_root_search_params{0.0f, 0.0f};
+    applyRootSearchConfig(r, bots[i].rs);
     bots[i].name = "bot" + std::to_string(i);
     r.gets("botName", bots[i].name);
     bots[i].model.clear();

@@ -108,6 +108,7 @@ bool gateOnce(const Settings& s, int gamesPerGating, const Dirs& d, bool autoRej
   must(coffee_match_create(&c, &h), "create match engine");
   must(coffee_match_set_uncertainty(h, &s.unc), "set uncertainty");  // one setting for both nets
   must(coffee_match_set_exploration(h, -1, &s.ex), "set exploration");  // likewise
+  must(coffee_match_set_root_search(h, -1, &s.rs), "set root search");
   if(s.unc.use_uncertainty)
     logf("gatekeeper: uncertainty weighting on for both nets: coeff %g, exponent %g, max weight %g",
          s.unc.uncertainty_coeff, s.unc.uncertainty_exponent, s.unc.uncertainty_max_weight);

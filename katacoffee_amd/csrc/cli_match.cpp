@@ -220,6 +220,10 @@ int matchMain(int argc, char** argv) {
   must(coffee_match_create2(&c, &o, &h), "create match engine");
   for(int i = 0; i < 2; i++) {
     must(coffee_match_set_exploration(h, i, &bots[i].ex), "set exploration");
+    must(coffee_match_set_root_search(h, i, &bots[i].rs), "set root search");
+    if(bots[i].rs.wide_root_noise > 0.0f || bots[i].rs.futile_visits_threshold > 0.0f)
+      logf("match: bot %d: wide root noise %g, futile visits threshold %g", i, bots[i].rs.wide_root_noise,
+           bots[i].rs.futile_visits_threshold);
     if(bots[i].ex.use_noise_pruning || bots[i].ex.cpuct_utility_stdev_scale != 0.0f)
       logf("match: bot %d: cpuct stdev scale %g (prior %g, weight %g), noise pruning %s", i,
            bots[i].ex.cpuct_utility_stdev_scale, bots[i].ex.cpuct_utility_stdev_prior,

@@ -207,6 +207,7 @@ static void runGpu(int gpu, int server, int perGpu, int slot, int share, const S
   check(coffee_selfplay_create(&c, &h), "create engine");
   check(coffee_selfplay_set_uncertainty(h, &s.unc), "set uncertainty");
   check(coffee_selfplay_set_exploration(h, &s.ex), "set exploration");
+  check(coffee_selfplay_set_root_search(h, &s.rs), "set root search");
   if(s.unc.use_uncertainty)
     logf("gpu %d.%d: uncertainty weighting on: coeff %g, exponent %g, max weight %g", gpu, server,
          s.unc.uncertainty_coeff, s.unc.uncertainty_exponent, s.unc.uncertainty_max_weight);

@@ -27,6 +27,7 @@
 #include "startpos.h"
 #include "uncertainty.h"
 #include "explore.h"
+#include "rootsearch.h"
 
 namespace kc {
 
@@ -416,6 +417,10 @@ struct SearchDev {
   // per-side match engine; a copy of ex on every other engine).  Off: the launchers never pick
   // those instantiations.
   Expl ex, ex1;
+  // wide root noise and futile-visit pruning (coffee_*_set_root_search; rootsearch.h, DESIGN.md
+  // 8h), read by the EXPL kernel instantiations only, at the root's selection: rs beside ex, rs1
+  // beside ex1.
+  RootSearch rs, rs1;
 };
 
 // Match play: the candidate (net 1) plays black (player 1) in game number n of global

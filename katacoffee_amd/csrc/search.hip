@@ -210,6 +210,8 @@ KC_D void bindGame(GV& v, const GameDev& s) {
 
 // The exploration block (explore.h) of the view's side: beside unc / unc1.
 KC_D const Expl& explOf(const GV& v) { return v.unc == &v.d.unc1 ? v.d.ex1 : v.d.ex; }
+// Likewise the root-search block (rootsearch.h).
+KC_D const RootSearch& rootSearchOf(const GV& v) { return v.unc == &v.d.unc1 ? v.d.rs1 : v.d.rs; }
 
 // MATCH with per-side settings: the visit limit of the search about to start is the next
 // mover's (setMoveLimits gave side 0's; match play has no cheap or reduced searches).
@@ -868,7 +870,7 @@ KC_D float exploreScaling(const SP& sp, float totalChildWeight) {
 // Also returns the chosen existing child's edge and the child's visits and flags,
 // broadcast from the lane that holds them (no reload of either after the choice).
 template <int NI, bool EXPL = false>
-KC_D int selectBest(const GV& v, int ni, const Node& n, const float* pol, bool isRoot, int& newPos,
+KC_D int selectBest(const GV& v, const GameDev& s, int ni, const Node& n, const float* pol, bool isRoot, int& newPos,
                     uint32_t* hasBits, const Edge& e0, Edge& ce, uint32_t& cVisits, uint32_t& cFlags) {
   const SP& sp = *v.sp;
   const int P = v.d.P;
@@ -919,6 +921,29 @@ KC_D int selectBest(const GV& v, int ni, const Node& n, const float* pol, bool i
   float scaling = exploreScaling(sp, total);
   if constexpr(EXPL)
     scaling = scaling * exploreStdevFactor(explOf(v), n.visits, n.weightSum, n.utilityAvg, n.utilitySqAvg);
+  // wide root noise and futile-visit pruning (rootsearch.h): the root only, behind
+  // wave-uniform tests.  The draws are each move's own (wideRootKey, its policy position).
+  float rsWide = 0.0f, rsThr = 0.0f, rsMaxW = 0.0f, rsWpv = 0.0f, rsLeft = 0.0f;
+  uint64_t rsKey = 0;
+  if constexpr(EXPL) {
+    if(isRoot) {
+      const RootSearch& rs = rootSearchOf(v);
+      rsWide = rs.wide;
+      rsThr = rs.thr;
+      if(rsWide > 0.0f)
+        rsKey = wideRootKey(s.rngSeed, s.root.turn, n.visits);
+      if(rsThr > 0.0f) {
+        // (masked children carry weight 0 and weights are never negative)
+        float m = 0.0f;
+#pragma unroll
+        for(int j = 0; j < NI; j++)
+          m = fmaxf(m, cw[j]);
+        rsMaxW = waveMax(m);
+        rsWpv = n.weightSum / (float)n.visits;
+        rsLeft = (float)(s.visitLimit - (int32_t)n.visits);
+      }
+    }
+  }
   float best = -__builtin_inff();
   int bestIdx = BIG;
 #pragma unroll
@@ -933,10 +958,22 @@ KC_D int selectBest(const GV& v, int ni, const Node& n, const float* pol, bool i
     else {
       float w = cw[j];
       float u = (cvis[j] == 0 || w <= 0.0f) ? fpu : cu[j];
-      if(isRoot && sp.rootDesiredCoeff > 0.0f && p > 0.0f && w < sqrtf((p * total) * sp.rootDesiredCoeff))
+      bool futile = false;
+      if constexpr(EXPL)
+        futile = rsThr > 0.0f && futileChild(rsThr, rsMaxW, rsWpv, rsLeft, ev[j].visits, cvis[j], w);
+      if(futile)
+        val = FUTILE_VALUE;
+      else if(isRoot && sp.rootDesiredCoeff > 0.0f && p > 0.0f && w < sqrtf((p * total) * sp.rootDesiredCoeff))
         val = 1e20f;
-      else
+      else {
+        if constexpr(EXPL) {
+          if(rsWide > 0.0f) {
+            u = wideUtility(u, wideBonus(rsWide, rsKey, (int)ev[j].move), pla);
+            p = wideSmoothedPrior(rsWide, p);
+          }
+        }
         val = (scaling * p) / (1.0f + w) + (pla == 2 ? u : -u);
+      }
     }
     if(val > best) {
       best = val;
@@ -989,7 +1026,23 @@ KC_D int selectBest(const GV& v, int ni, const Node& n, const float* pol, bool i
   }
   newPos = -1;
   if(bpos != BIG) {
-    float val = (scaling * bp) / 1.0f + (pla == 2 ? fpu : -fpu);
+    float val;
+    bool futile = false;
+    if constexpr(EXPL)
+      futile = rsThr > 0.0f && futileNew(rsThr, rsMaxW, rsWpv, rsLeft);
+    if(futile)
+      val = FUTILE_VALUE;
+    else {
+      float u = fpu;
+      if constexpr(EXPL) {
+        // (the candidate stays the move of the largest raw prior; one draw, every lane the same)
+        if(rsWide > 0.0f) {
+          u = wideUtility(u, wideBonus(rsWide, rsKey, bpos), pla);
+          bp = wideSmoothedPrior(rsWide, bp);
+        }
+      }
+      val = (scaling * bp) / 1.0f + (pla == 2 ? u : -u);
+    }
     if(val > best) {
       bestSlot = k;
       newPos = bpos;
@@ -1090,8 +1143,8 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
     // a node with at most 64 children (every non-root level in practice, the root until
     // its 65th child) takes the one-item form: an empty second item adds nothing to the
     // sums and never wins the (value, index) argmax, so the results are the same
-    int slot = n.numChildren <= 64 ? selectBest<1, EXPL>(v, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags)
-                                   : selectBest<NI, EXPL>(v, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags);
+    int slot = n.numChildren <= 64 ? selectBest<1, EXPL>(v, s, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags)
+                                   : selectBest<NI, EXPL>(v, s, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags);
     SPROF_ADD(5, SPROF_NOW() - tSel);
     (void)tSel;
     if(slot < 0) {
@@ -4854,7 +4907,9 @@ static void launchEv(K kernel, dim3 grid, dim3 block, uint32_t lds, hipStream_t 
 // Whether the engine's searches carry variance-scaled exploration or noise pruning (explore.h;
 // DESIGN.md 8g): the launchers then take the EXPL instantiations, every other engine the ones
 // without them, which hold no trace of either mechanism.
-static bool explLaunch(const SearchDev& d) { return explOn(d.ex) || explOn(d.ex1); }
+static bool explLaunch(const SearchDev& d) {
+  return explOn(d.ex) || explOn(d.ex1) || rootSearchOn(d.rs) || rootSearchOn(d.rs1);
+}
 
 // KERNEL<NI, ...> by the engine's items per lane.
 #define KC_BY_ITEMS(LAUNCH, KERNEL, ...)                         \

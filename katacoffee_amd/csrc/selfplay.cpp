@@ -136,6 +136,15 @@ Expl toExpl(const coffee_exploration_params& p) {
               p.cpuct_utility_stdev_prior, p.cpuct_utility_stdev_prior_weight, p.cpuct_utility_stdev_scale};
 }
 
+RootSearch toRootSearch(const coffee_root_search_params& p) {
+  // (the comparisons also reject NaN and +inf)
+  if(!(p.wide_root_noise >= 0.0f && p.wide_root_noise <= 5.0f))
+    throw std::invalid_argument("wide_root_noise must be in [0, 5]");
+  if(!(p.futile_visits_threshold == 0.0f || (p.futile_visits_threshold >= 0.01f && p.futile_visits_threshold <= 1.0f)))
+    throw std::invalid_argument("futile_visits_threshold must be 0 or in [0.01, 1]");
+  return RootSearch{p.wide_root_noise, p.futile_visits_threshold};
+}
+
 void validateMatchConfig(const coffee_match_config& c) {
   if(c.x < 2 || c.y < 2 || c.x > MAX_LEN || c.y > MAX_LEN)
     throw std::invalid_argument("board size must be 2..10 x 2..10");
@@ -519,6 +528,8 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* cons
     coffee_exploration_params_default(&e);
     d.ex = toExpl(e);  // off
     d.ex1 = d.ex;
+    d.rs = RootSearch{0.0f, 0.0f};  // off
+    d.rs1 = d.rs;
   }
   d.sp1 = d.sp;
   if(perSide) {
@@ -723,6 +734,24 @@ void SelfplayEngine::setExploration(int side, const coffee_exploration_params& p
   // nothing runs yet (the constructor synchronised its initialisation): plain copies
   KC_HIP(hipMemcpy(&dd_->ex, &hd_.ex, sizeof(Expl), hipMemcpyHostToDevice));
   KC_HIP(hipMemcpy(&dd_->ex1, &hd_.ex1, sizeof(Expl), hipMemcpyHostToDevice));
+}
+
+void SelfplayEngine::setRootSearch(int side, const coffee_root_search_params& p) {
+  const RootSearch r = toRootSearch(p);
+  if(hd_.matchPerSide ? (side != 0 && side != 1) : side != -1)
+    throw std::invalid_argument(hd_.matchPerSide ? "set_root_search: side must be 0 or 1 on an engine with per-side settings"
+                                                 : "set_root_search: side must be -1 on an engine without per-side settings");
+  // like set_exploration: a tree must never mix the two rules
+  if(rounds_ > 0 || aSubmitted_ > 0)
+    throw std::invalid_argument(hd_.analysisMode ? "set_root_search: only before the first query and round"
+                                                 : "set_root_search: only before the engine's first round");
+  if(side != 1)
+    hd_.rs = r;
+  if(side != 0)
+    hd_.rs1 = r;
+  // nothing runs yet (the constructor synchronised its initialisation): plain copies
+  KC_HIP(hipMemcpy(&dd_->rs, &hd_.rs, sizeof(RootSearch), hipMemcpyHostToDevice));
+  KC_HIP(hipMemcpy(&dd_->rs1, &hd_.rs1, sizeof(RootSearch), hipMemcpyHostToDevice));
 }
 
 void SelfplayEngine::setRootOptions(const coffee_analysis_root_options& o) {

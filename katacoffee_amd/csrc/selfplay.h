@@ -19,6 +19,10 @@ Unc toUnc(const coffee_uncertainty_params& p);
 // reference's ranges (setup.cpp:453-470, :520-537), for a non-finite value and for prior 0 with
 // scale > 0.
 Expl toExpl(const coffee_exploration_params& p);
+// The device block of coffee_root_search_params; throws std::invalid_argument outside the
+// reference's ranges (wideRootNoise [0, 5]; futileVisitsThreshold 0 or [0.01, 1]) and for a
+// non-finite value.
+RootSearch toRootSearch(const coffee_root_search_params& p);
 // Start positions: the parameters' ranges; the thresholds of a table on the host (startpos.h);
 // the check kernel on a host table at a geometry.  Each throws std::invalid_argument naming
 // the setting or the first bad sample.
@@ -64,6 +68,7 @@ class SelfplayEngine {
   void setUncertainty(const coffee_uncertainty_params& p);
   // side: -1 on an engine without per-side settings, 0 / 1 on one with them
   void setExploration(int side, const coffee_exploration_params& p);
+  void setRootSearch(int side, const coffee_root_search_params& p);
   // Start positions: checks the parameters and every sample (kStartPosCheck),
   // builds the thresholds and uploads both once the engine stream is idle; between steps at any time.
   // Throws std::invalid_argument (naming the first bad sample) with the engine untouched.

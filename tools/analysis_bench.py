@@ -72,6 +72,8 @@ def main():
     ap.add_argument("--exploration", action="store_true",
                     help="the reference's match / analysis exploration: cpuctUtilityStdevScale 0.85 and noise pruning "
                          "(set_exploration) in both engines")
+    ap.add_argument("--root-search", action="store_true",
+                    help="wide root noise 0.04 and futile-visit pruning at threshold 0.15 (set_root_search) in both engines")
     ap.add_argument("--root-symmetry-pruning", action="store_true",
                     help="root symmetry pruning on in the analysis engine")
     a = ap.parse_args()
@@ -86,6 +88,8 @@ def main():
         an.set_uncertainty(use_uncertainty=int(a.uncertainty))
         if a.exploration:
             an.set_exploration(**dict(cpuct_utility_stdev_scale=0.85, use_noise_pruning=1))
+        if a.root_search:
+            an.set_root_search(wide_root_noise=0.04, futile_visits_threshold=0.15)
         has_root = hasattr(kc.lib(), "coffee_root_mask")  # (absent in earlier builds run as A/B references)
         if a.root_symmetry_pruning:
             an.set_root_options(root_symmetry_pruning=True)
@@ -137,6 +141,8 @@ def main():
         sp.set_uncertainty(use_uncertainty=int(a.uncertainty))
         if a.exploration:
             sp.set_exploration(**dict(cpuct_utility_stdev_scale=0.85, use_noise_pruning=1))
+        if a.root_search:
+            sp.set_root_search(wide_root_noise=0.04, futile_visits_threshold=0.15)
         sp.step(a.warmup)
         sp.sync()
         sp.drain_rows()

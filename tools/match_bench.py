@@ -60,6 +60,8 @@ def main():
     ap.add_argument("--exploration", action="store_true",
                     help="the reference's match / analysis exploration: cpuctUtilityStdevScale 0.85 and noise pruning "
                          "(set_exploration) in both engines")
+    ap.add_argument("--root-search", action="store_true",
+                    help="wide root noise 0.04 and futile-visit pruning at threshold 0.15 (set_root_search) in both engines")
     ap.add_argument("--equal-sides", action="store_true",
                     help="per-side settings with both sides the engine's own parameters (kc.Match(sides=...))")
     ap.add_argument("--share-net", action="store_true",
@@ -87,6 +89,9 @@ def main():
         if a.exploration:
             for side in ((0, 1) if a.equal_sides else (-1,)):
                 m.set_exploration(side=side, **dict(cpuct_utility_stdev_scale=0.85, use_noise_pruning=1))
+        if a.root_search:
+            for side in ((0, 1) if a.equal_sides else (-1,)):
+                m.set_root_search(side=side, wide_root_noise=0.04, futile_visits_threshold=0.15)
         msecs, mgames, mst = timed(m, a.rounds, a.warmup, a.repeats, m.drain_games)
         m.close()
         over.pop("max_visits")
@@ -94,6 +99,8 @@ def main():
         s.set_uncertainty(use_uncertainty=int(a.uncertainty))
         if a.exploration:
             s.set_exploration(**dict(cpuct_utility_stdev_scale=0.85, use_noise_pruning=1))
+        if a.root_search:
+            s.set_root_search(wide_root_noise=0.04, futile_visits_threshold=0.15)
 
         def drain_sp():
             s.drain_rows()
