@@ -33,10 +33,7 @@ constexpr int NN_BOARDS_PER_WG = 8;
 // CU): 5 boards = 125 positions fill the 128 rows its 8 waves compute as exactly as 4
 // (100 rows) do, so a launch takes one workgroup's latency on a fifth fewer CUs; the
 // other game group's search waves take the free CUs (nn.hip NNGeo).
-#ifndef NN_SMALL_BOARDS
-#define NN_SMALL_BOARDS 5
-#endif
-constexpr int NN_SMALL_NB = NN_SMALL_BOARDS;
+constexpr int NN_SMALL_NB = 5;
 // Offsets (elements) into the packed weight buffers; see nn.hip.
 constexpr int NN_MAX_BLOCKS = 16;
 struct NNLayout {
@@ -187,7 +184,6 @@ class NNEngine {
   uint16_t* tabDevS_ = nullptr;  // the same for the 2-board split instance (NN_ACCURATE_NB2)
   uint16_t* tabDevB_ = nullptr;  // the same for the borderless 5-board instances (accurate, corrected)
   int mode_ = NN_FAST;           // NNPath of the fused kernel
-  int small_ = 0;                // KATACOFFEE_NN_SMALL=8: small batches on the 8-board instance (A/B runs)
   float* trunk_ = nullptr;       // f32 residual trunk scratch, [workgroup][fragment] (nn.hip)
   size_t trunkBytes_ = 0;        // its size
   int cus_ = 1;                  // compute units of the engine's device

@@ -69,64 +69,39 @@ constexpr float F8C_MAX = 448.0f;  // largest finite e4m3fn
 // game group fits on each SIMD beside its two network waves (2 x 192 + 128 = 512):
 // it is compiled separately (nn_corr.hip) as kNNForwardCap with amdgpu_num_vgpr
 // KC_F8C_VGPR, which gfx950 counts in register pairs (96 = 192 VGPRs; 0: uncapped, the
-// plain kNNForward instance).  KC_F8C_PARK 1: the f32 trunk is parked in the
-// workgroup-private global scratch during a block's first conv (24 registers);
-// KC_F8C_LATE 1: a K-step's fragments are read after the previous step's MFMAs issue
-// (one fragment buffer).  (A/B builds: tools/Makefile alt, ALT_FLAGS=-DKC_F8C_VGPR=0 ...)
+// plain kNNForward instance, which tools/Makefile builds the phase tools with).  The
+// accurate (split) borderless instance runs under the same cap (222 VGPRs uncapped: no
+// search wave of the other game group fits beside it).
 // Measured (C2 corrected bench, one box, 20 steps): uncapped 19.0 k rows/s (network 144 us,
-// other group's select 105 us: no room beside the network's 233-256-VGPR waves); capped +
-// late 19.5 k (network 163 us, select 71 us, backup 50 -> 59 us: the search waves now share
-// the network's CUs); capped + late + parked trunk 19.3 k; late + parked, uncapped 18.1 k.
-// Second box: capped + late 19.4 k, capped + parked 19.3 k, capped alone 19.7 k (network
-// 154 us; 49 registers spilled, reloaded outside the K loops): the default.
+// other group's select 105 us: no room beside the network's 233-256-VGPR waves); capped,
+// with a K-step's fragments read after the previous step's MFMAs issue (one fragment
+// buffer), 19.5 k (network 163 us, select 71 us, backup 50 -> 59 us: the search waves now
+// share the network's CUs); that plus the f32 trunk parked in the workgroup-private global
+// scratch during a block's first conv (24 registers) 19.3 k; both of those uncapped 18.1 k.
+// Second box: capped + late reads 19.4 k, capped + parked trunk 19.3 k, capped alone 19.7 k
+// (network 154 us; 49 registers spilled, reloaded outside the K loops): what is built.
+// The same late reads in the accurate borderless instance (round 6,
+// profiles/r06/acc_late_ab.txt): 182 VGPRs and no spills against 17 spilled, but the network
+// alone 3 % slower and the C2 bench equal within noise; it stays double-buffered.
 #ifndef KC_F8C_VGPR
 #define KC_F8C_VGPR 96
 #endif
-// KC_ACC_CAP 1: the accurate (split) borderless instance runs under the same cap (222 VGPRs
-// uncapped: no search wave of the other game group fits beside it); 0: uncapped (A/B)
-#ifndef KC_ACC_CAP
-#define KC_ACC_CAP 1
-#endif
-// KC_ACC_LATE 1: the accurate borderless instance reads a K-step's fragments after the
-// previous step's MFMAs issue (one fragment buffer, like KC_F8C_LATE); 0: double-buffered.
-// Measured (round 6, profiles/r06/acc_late_ab.txt): 182 VGPRs and no spills against 17 spilled,
-// but the network alone 3 % slower and the C2 bench equal within noise: off
-#ifndef KC_ACC_LATE
-#define KC_ACC_LATE 0
-#endif
-#ifndef KC_F8C_PARK
-#define KC_F8C_PARK 0
-#endif
-#ifndef KC_F8C_LATE
-#define KC_F8C_LATE 0
-#endif
-// KC_F8C_CVTW 1: the weights' e4m3(hi(w) 2^-sw) is converted from the fp16 fragments in
-// registers (the ring slot holds fp16 hi + e4m3 lo(w): 27 KiB per 96-channel tap), 0: the
-// slot holds host-packed e4m3 [lo(w) | hi(w)] pairs (36 KiB).  KC_F8C_CVTX 1: e4m3(hi(x))
-// is converted from the activation fragments (the second plane holds e4m3 lo(x) only, one
-// byte per channel), 0: the plane holds [hi(x) | lo(x)] pairs.  Either conversion frees
-// the LDS for a 3-slot weight ring (both off: the 2-slot ring, the default).  Measured
-// (round 5, tools/ab_nn.sh, 960 boards): 2-slot 153 us; both converted 191-348 us
-// (register pressure: 72-96 spilled VGPRs under the cap), activations only 186 us,
-// weights only 331 us.  tools/cvt_rate.hip: one v_cvt_scalef32_pk_fp8_f16 costs 13.8
+// The corrected instance's ring slot holds host-packed e4m3 [lo(w) | hi(w)] pairs after the
+// fp16 fragments (36 KiB per 96-channel tap) and its second activation plane [hi(x) | lo(x)]
+// pairs: a 2-slot ring.  Converting e4m3(hi(w)) and / or e4m3(hi(x)) from the fp16
+// fragments in registers instead frees the LDS for a 3-slot ring of 27 KiB slots; measured
+// (round 5, tools/ab_nn.sh, 960 boards): 2-slot 153 us; both converted
+// 191-348 us (register pressure: 72-96 spilled VGPRs under the cap), activations only
+// 186 us, weights only 331 us.  tools/cvt_rate.hip: one v_cvt_scalef32_pk_fp8_f16 costs 13.8
 // cycles per wave at 2 waves per SIMD (v_add_f32: 5.1) and each adds ~11 cycles to the
 // K-step's MFMA stream -- it does not co-issue beside the MFMAs, so the 8-20 conversions
 // per K-step cost more than the deeper ring and the smaller LDS footprint save.
-#ifndef KC_F8C_CVTW
-#define KC_F8C_CVTW 0
-#endif
-// KC_FAST_BL 1: the fast (fp16) small-batch instance is borderless too, with ring slots of
-// three taps (one barrier per three taps instead of per pair; 192-VGPR cap, 17 spilled;
-// the branch scratch in ring slot 1); 0: the bordered 5-board instance with the paired
-// 4-slot ring (rounds 3-4, the default).  Measured (round 5, same box): network alone
-// 77.7 vs 75.3 us at 960 boards, C2 bench 22.9-23.1 k vs 24.0 k rows/s (in-bench network
-// 94 vs 84 us: its 149 KB of LDS leaves the other group's search blocks less room).
-#ifndef KC_FAST_BL
-#define KC_FAST_BL 0
-#endif
-#ifndef KC_F8C_CVTX
-#define KC_F8C_CVTX 0
-#endif
+// The fast (fp16) small-batch instance is the bordered 5-board one with the paired 4-slot
+// ring (rounds 3-4).  A borderless one with ring slots of three taps (one barrier per three
+// taps instead of per pair; 192-VGPR cap, 17 spilled) was measured in round 5, same box:
+// network alone 77.7 vs 75.3 us at 960 boards, C2 bench 22.9-23.1 k vs 24.0 k rows/s
+// (in-bench network 94 vs 84 us: its 149 KB of LDS leaves the other group's search blocks
+// less room).
 constexpr float F8C_SCALE = 2048.0f;  // 2^F8C_SHIFT
 // Block exponent of the corrected precision's e4m3 weights (oracle/ora_nn.cpp f8Exp, the
 // same integer arithmetic): m 2^-s in (224, 448] for m > 0 (m = f 2^e, f in [0.5, 1):
@@ -168,14 +143,11 @@ struct NNGeo {
   // pair j+1 is requested at the start of pair j and published by one barrier per pair.
   // 2 (BL split): chunks (one 36 KiB slot: a 96-channel tap, or 3 stem taps) alternate;
   // chunk j+2 is requested right after the barrier that publishes chunk j+1 and frees
-  // chunk j.  3 (BL corrected: 27 KiB slots, the e4m3 weights derived from the fp16
-  // fragments in registers): chunk j+3 is requested after that barrier, so a chunk's DMA
-  // has two chunks of MFMAs to land in.  (6 slots, one barrier per 3 taps, would fill all
-  // 160 KiB and keep the other game group's search kernels off the CU while the network
-  // runs.)
-  static constexpr bool F8W = MODE_ == NN_MODE_F8C && KC_F8C_CVTW;  // e4m3(w) converted in registers
-  static constexpr bool F8X = MODE_ == NN_MODE_F8C && KC_F8C_CVTX;  // e4m3(x) converted in registers
-  static constexpr int RING = BL ? ((F8W || F8X) ? 3 : 2) : ((NB_ == NN_SMALL_NB && !SPLIT) ? 4 : 3);
+  // chunk j.  (A 3-slot BL ring of 27 KiB slots, the corrected instance's e4m3 operands
+  // converted from the fp16 fragments in registers, was measured at 186-348 us against
+  // 153 us: DESIGN.md §3a.)
+  static_assert(!BL || SPLIT, "borderless instances are split (accurate or corrected), never NN_MODE_F16");
+  static constexpr int RING = BL ? 2 : ((NB_ == NN_SMALL_NB && !SPLIT) ? 4 : 3);
   static constexpr bool PAIRS = RING == 4;
   static constexpr int ROWS = NB * A;
   static constexpr int RT = (ROWS + 15) / 16;
@@ -199,12 +171,9 @@ struct NNGeo {
   static constexpr int NCT_ALL = C / 16;
   static constexpr int P = 4 * A;
   static constexpr int PLANE_BYTES = (PROWS * ROWB + 15) / 16 * 16;  // the hi plane
-  // the second plane: fp16 lo values (mode 1, rows like the hi plane); e4m3(lo(x) 2^11)
-  // (mode 2: one byte per channel, rows of ROWB / 2 bytes, so a lane's address there is
-  // half its hi-plane address; e4m3(x) is converted from the hi fragment in registers)
-  static constexpr int ROWB2 = F8X ? ROWB / 2 : ROWB;
-  static constexpr int PLANE2_BYTES = SPLIT ? (PROWS * ROWB2 + 15) / 16 * 16 : 0;
-  static constexpr int ACT_BYTES = PLANE_BYTES + PLANE2_BYTES;
+  // the second plane, rows like the hi plane: fp16 lo values (mode 1), or per channel octet
+  // the 16 bytes [e4m3(hi(x)) | e4m3(lo(x) 2^11)] (mode 2)
+  static constexpr int ACT_BYTES = PLANES * PLANE_BYTES;
   // f32 [MROWS][SCR] scratch for the g / value branches: aliases act (dead then)
   static constexpr int SCR = 36;  // f32 scratch row stride: 4-row lane groups hit distinct banks
   // (at least the gpool linear weights' [96][64] f32, staged below it)
@@ -212,14 +181,12 @@ struct NNGeo {
   static constexpr int OFF_POOL = ACT_BYTES;
   static constexpr int OFF_BIAS = OFF_POOL + 2 * NB * 96 * 4;
   static constexpr int WBUF = (C / 32) * NCT_ALL * 64;  // 16-B weight fragments per tap and plane
-  // a tap's second weight block: fp16 lo fragments (mode 1); e4m3(lo(w) 2^(11-sw)) only, 8 B
-  // per lane and fragment (mode 2: e4m3(w 2^-sw) is converted from the hi fragment)
-  static constexpr int WBUF2 = !SPLIT ? 0 : (F8W ? WBUF / 2 : WBUF);
-  // one ring slot (16-B units): a tap's blocks, or three fp16 taps (fast borderless)
-  static constexpr int WSLOT = (BL && !SPLIT) ? 3 * WBUF : WBUF + WBUF2;
+  // one ring slot (16-B units): a tap's hi block and (SPLIT) its second block of the same
+  // size -- fp16 lo fragments (mode 1), or e4m3 [lo(w) 2^(11-sw) | hi(w) 2^-sw] pairs (mode 2)
+  static constexpr int WSLOT = PLANES * WBUF;
   static constexpr int SLOT_PIECES = WSLOT / 64;  // its 1-KiB pieces
   // 1-KiB pieces of one tap of a conv with ncb 32-channel input blocks
-  static constexpr int tapPieces(int ncb) { return ncb * NCT_ALL * (!SPLIT ? 2 : (F8W ? 3 : 4)) / 2; }
+  static constexpr int tapPieces(int ncb) { return ncb * NCT_ALL * PLANES; }
   // BL ring chunks of a conv with ntaps taps of ncb blocks: taps per chunk, chunks, and the
   // pieces of its first chunk (what the previous conv requests ahead)
   static constexpr int chunkTaps(int ncb, int ntaps) {
@@ -240,16 +207,8 @@ struct NNGeo {
   static constexpr int OFF_PRM = (OFF_DST + NB * 4 + 15) / 16 * 16;
   static constexpr int OFF_W = OFF_PRM + 2 * NPRM * 4;
   static constexpr int LDS = OFF_W + RING * WSLOT * 16;
-  // the f32 scratch of the g / value branches: in act (dead then), or -- fast borderless,
-  // whose one-plane act is too small -- in ring slot 1, which holds only a consumed chunk
-  // during the gpool mids (conv1's last chunk; conv2's first is in slot 0) and the heads
-  // (the head conv's chunk; the heads' linear weights use slot 0)
-  static constexpr bool SCR_IN_RING = BL && !SPLIT;
-  static constexpr int SCR_OFF = SCR_IN_RING ? OFF_W + WSLOT * 16 : OFF_SCR;
   static_assert(C % 32 == 0, "C must be a multiple of 32");
-  static_assert(SCR_IN_RING ? (MROWS * SCR * 4 <= WSLOT * 16 && RING == 2 && RING_VH + NB * 64 * 4 <= WSLOT * 16)
-                            : OFF_SCR + MROWS * SCR * 4 <= ACT_BYTES,
-                "f32 branch scratch must fit in act (or in ring slot 1)");
+  static_assert(OFF_SCR + MROWS * SCR * 4 <= ACT_BYTES, "f32 branch scratch must fit in act");
   static_assert(96 * 64 * 4 <= OFF_SCR, "gpool linear weights must fit below scr");
   static_assert(RING * WSLOT * 16 >= RING_VH + NB * 64 * 4, "head linear weights and vh must fit in the ring");
   static_assert((PLANES - 1) * PLANE_BYTES + (BL ? 0 : 2 * PA * ROWB) + 2 * 64 < 65536,
@@ -470,8 +429,6 @@ KC_D void convTiles(const uint16_t* __restrict__ act, const h16x8* __restrict__ 
 // ---- borderless (BL) instances ----------------------------------------------
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h2x __attribute__((ext_vector_type(2)));
 
 // Per tile: the byte address of this lane's A-fragment row (row r = output row r, plus
 // the lane's k-quarter) and a 9-bit mask of the 3x3 taps whose neighbour is on the
@@ -502,25 +459,23 @@ KC_D void stageChunk(const h16x8* __restrict__ src, uint32_t slotAddr, int piece
 }
 
 // Implicit-GEMM convolution of a BL instance, computed transposed like convTiles.
-// Weights stream through the RING-slot ring in chunks of TPC taps (one slot: a 96-channel
-// tap, or three stem taps); chunk j of this conv lives in slot (PAR + j) % RING, PAR the
-// index mod RING of the conv's first chunk in the whole stream.  On entry chunks
-// 0 .. RING-2 were requested and are resident and published (the caller retired its DMA
-// before the barrier that published the conv's input), and the slot of chunk RING-1 is
-// free: it is requested at once.  One barrier per chunk, before the chunk's last K-step:
-// every wave retires its pieces of chunk j+1 (the younger requests -- chunk j+2 with three
-// slots -- stay in flight: a counted vmcnt), the barrier publishes them and frees chunk j's
-// slot (all its fragment reads are complete: lgkmcnt(0)), and chunk j+RING is requested
-// into it (this conv's, or the next conv's chunk j+RING-NCH: nextPieces pieces each,
+// Weights stream through the 2-slot ring in chunks of TPC taps (one slot: a 96-channel
+// tap, or three stem taps); chunk j of this conv lives in slot (PAR + j) % 2, PAR the
+// parity of the conv's first chunk in the whole stream.  On entry chunk 0 was requested
+// and is resident and published (the caller retired its DMA before the barrier that
+// published the conv's input), and the slot of chunk 1 is free: it is requested at once.
+// One barrier per chunk, before the chunk's last K-step: every wave retires its pieces of
+// chunk j+1 (nothing younger is in flight), the barrier publishes them and frees chunk j's
+// slot (all its fragment reads are complete: lgkmcnt(0)), and chunk j+2 is requested
+// into it (this conv's, or the next conv's chunk j+2-NCH: nextPieces pieces each,
 // nextNCH chunks).  A-fragment addresses are formed per tap: the neighbour row, or the
 // zero row when the neighbour is off the board.
 //   MODE 1: acc += hi(w) hi(x) + lo(w) hi(x) + hi(w) lo(x)  (three f16 MFMAs per step)
 //   MODE 2: acc += hi(w) hi(x) per step (f16 MFMA), and per pair of steps one scaled e4m3
 //           MFMA over [lo(w) 2^(11-sw) | hi(w) 2^-sw] x [hi(x) | lo(x) 2^11] of both steps,
-//           A scale 2^(sw-11): lo(w) and lo(x) are read from the second weight block /
-//           activation plane (8 bytes per lane and fragment), e4m3 of the hi fragments
-//           is converted in registers (v_cvt_scalef32_pk_fp8_f16, which divides by its
-//           scale: 2^sw for the weights, 1 for the activations).
+//           A scale 2^(sw-11): both e4m3 pairs are read from the second weight block /
+//           activation plane (16 bytes per lane and fragment; the weights' packed on the
+//           host, the activations' stored by the epilogues).
 //   sA (mode 2): the A operand's E8M0 scale byte, 127 - 11 + the conv's weight exponent sw.
 // DBG (tools/convb_bench.hip ablations only): bit 0 skips the weight requests, bit 1 the
 // chunk waits and barriers, bit 2 the scaled e4m3 MFMAs, bit 3 the second-plane fragment
@@ -536,10 +491,9 @@ KC_D void convTilesB(const uint16_t* __restrict__ act, const h16x8* __restrict__
   static_assert(TPC * CH <= G::SLOT_PIECES, "a tap must fit one ring slot");
   constexpr int NCH = (NTAPS + TPC - 1) / TPC;
   constexpr int STEPS = NTAPS * NCB;
-  constexpr int R = G::RING;
+  constexpr int R = G::RING;  // 2
+  static_assert(G::BL && R == 2, "the borderless instances' 2-slot ring");
   constexpr bool F8C = G::MODE == NN_MODE_F8C;
-  // fewest pieces any wave issues for a chunk of the next conv (a 64-channel tap: 2 blocks)
-  constexpr int NEXT_MIN = G::tapPieces(2) / G::NW;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t ring = ldsAddr(wl);
   auto slotOf = [&](int j) { return (PAR + j) % R; };
@@ -558,7 +512,7 @@ KC_D void convTilesB(const uint16_t* __restrict__ act, const h16x8* __restrict__
   const char* actB = reinterpret_cast<const char*>(act);
   const int zb = G::ZROW * G::ROWB + 16 * (lane >> 4);
   const h16x8* wlane = wl + (cg * G::NCT) * 64 + lane;
-  int at[G::MAXT];  // this tap's A-fragment row addresses (hi plane; mode 2's plane: half)
+  int at[G::MAXT];  // this tap's A-fragment row addresses (either plane)
   auto tapAddr = [&](int tap) {
     const int tb = NTAPS == 9 ? tap : 4;  // 1x1: the centre tap
     const int off = ((tb / 3 - 1) * G::X + (tb % 3 - 1)) * G::ROWB;
@@ -570,82 +524,39 @@ KC_D void convTilesB(const uint16_t* __restrict__ act, const h16x8* __restrict__
   // second planes: fp16 lo fragments, double buffered (mode 1); e4m3 (mode 2), the two
   // steps of an MFMA pair in the low / high half of one 8-register operand, so the scaled
   // MFMA reads its operands in place (the halves are the double buffer): per step
-  // bq = [lo(w) (loaded) | hi(w) (converted)], aq = [hi(x) (converted) | lo(x) (loaded)]
+  // bq = [lo(w) | hi(w)], aq = [hi(x) | lo(x)]
   h16x8 afl[G::MODE == NN_MODE_SPLIT3 ? 2 : 1][G::MAXT], bfl[G::MODE == NN_MODE_SPLIT3 ? 2 : 1][G::NCT];
   i32x8 aq[G::MAXT], bq[G::NCT];
-  // 2^sw: the weights' conversion scale (the conversion divides by it)
-  const float wScale = __builtin_bit_cast(float, (uint32_t)(sA - 127 + F8C_SHIFT + 127) << 23);
   auto loadStep = [&](int st, int buf) {
     const int tap = st / NCB, cb = st - tap * NCB;
     const int chunk = tap / TPC, tc = tap - chunk * TPC;
-    const int slot = slotOf(chunk);
-    const h16x8* wb = wlane + slot * G::WSLOT + tc * CH * 64 + cb * G::NCT_ALL * 64;
+    const h16x8* wb = wlane + slotOf(chunk) * G::WSLOT + tc * CH * 64 + cb * G::NCT_ALL * 64;
 #pragma unroll
     for(int ct = 0; ct < G::NCT; ct++) {
       bf[buf][ct] = wb[ct * 64];
-      if constexpr((DBG & 8) || G::MODE == NN_MODE_F16) {
+      if constexpr(DBG & 8) {
       } else if constexpr(G::MODE == NN_MODE_SPLIT3) {
         bfl[buf][ct] = wb[CHP * 64 + ct * 64];
-      } else if constexpr(!G::F8W) {
+      } else {
         const i32x4 v = __builtin_bit_cast(i32x4, wb[CHP * 64 + ct * 64]);  // [lo(w) | w] pairs
         if(buf)
           bq[ct].hi = v;
         else
           bq[ct].lo = v;
-      } else {
-        // this lane's 8 bytes of the fragment in the tap's e4m3 block (512 B per fragment)
-        const int frag = cb * G::NCT_ALL + cg * G::NCT + ct;
-        const int2 v = *reinterpret_cast<const int2*>(reinterpret_cast<const char*>(wl) +
-                                                      (size_t)(slot * G::WSLOT + tc * CH * 64) * 16 + CHP * 1024 +
-                                                      frag * 512 + lane * 8);
-        bq[ct][4 * buf] = v.x;
-        bq[ct][4 * buf + 1] = v.y;
       }
     }
 #pragma unroll
     for(int t = 0; t < G::MAXT; t++) {
       af[buf][t] = *reinterpret_cast<const h16x8*>(actB + at[t] + cb * 64);
-      if constexpr((DBG & 8) || G::MODE == NN_MODE_F16) {
+      if constexpr(DBG & 8) {
       } else if constexpr(G::MODE == NN_MODE_SPLIT3) {
         afl[buf][t] = *reinterpret_cast<const h16x8*>(actB + G::PLANE_BYTES + at[t] + cb * 64);
-      } else if constexpr(!G::F8X) {
+      } else {
         const i32x4 v = __builtin_bit_cast(i32x4, *reinterpret_cast<const h16x8*>(actB + G::PLANE_BYTES + at[t] + cb * 64));
         if(buf)
           aq[t].hi = v;
         else
           aq[t].lo = v;
-      } else {
-        const int2 v = *reinterpret_cast<const int2*>(actB + G::PLANE_BYTES + (at[t] >> 1) + cb * 32);
-        aq[t][4 * buf + 2] = v.x;
-        aq[t][4 * buf + 3] = v.y;
-      }
-    }
-  };
-  // mode 2: e4m3 of a step's hi fragments (8 fp16 values -> 8 bytes in two registers)
-  auto e4m3x8 = [](const h16x8& h, float scale, int oldA, int oldB) {
-    // (both halves of each register are written: the old contents only save a zeroing move)
-    s16x2 a = __builtin_bit_cast(s16x2, oldA), b = __builtin_bit_cast(s16x2, oldB);
-    a = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(a, h2x{h[0], h[1]}, scale, false);
-    a = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(a, h2x{h[2], h[3]}, scale, true);
-    b = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(b, h2x{h[4], h[5]}, scale, false);
-    b = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(b, h2x{h[6], h[7]}, scale, true);
-    return int2{__builtin_bit_cast(int, a), __builtin_bit_cast(int, b)};
-  };
-  auto convertStep = [&](int buf) {
-    if constexpr(G::F8W) {
-#pragma unroll
-      for(int ct = 0; ct < G::NCT; ct++) {
-        const int2 v = e4m3x8(bf[buf][ct], wScale, bq[ct][4 * buf + 2], bq[ct][4 * buf + 3]);
-        bq[ct][4 * buf + 2] = v.x;
-        bq[ct][4 * buf + 3] = v.y;
-      }
-    }
-    if constexpr(G::F8X) {
-#pragma unroll
-      for(int t = 0; t < G::MAXT; t++) {
-        const int2 v = e4m3x8(af[buf][t], 1.0f, aq[t][4 * buf], aq[t][4 * buf + 1]);
-        aq[t][4 * buf] = v.x;
-        aq[t][4 * buf + 1] = v.y;
       }
     }
   };
@@ -666,36 +577,22 @@ KC_D void convTilesB(const uint16_t* __restrict__ act, const h16x8* __restrict__
     const int chunk = tap / TPC;
     const bool chunkEnd = cb == NCB - 1 && (tap == NTAPS - 1 || (tap + 1) % TPC == 0);
     if(chunkEnd && chunk + 1 < NCH && !(DBG & 2)) {
-      // retire this wave's pieces of chunk+1 (with three slots chunk+2's requests, at
-      // least NW2 per wave, may stay in flight), publish them, free chunk's slot, request
+      // retire this wave's pieces of chunk+1, publish them, free chunk's slot, request
       // chunk+R
-      if constexpr(DBG & 32) {
-      } else if constexpr(R == 3) {
-        // (chunk is a constant after unrolling: one branch remains; the next conv's chunk
-        // exists unless nextPieces / nextNCH say otherwise -- then nothing younger is in
-        // flight and every request must be retired)
-        static_assert(NTAPS % TPC == 0, "three-slot ring: whole chunks");
-        if(chunk + 2 < NCH)
-          waitVm<TPC * CH / G::NW>();
-        else if(nextPieces > 0 && chunk + 2 - NCH < nextNCH)
-          waitVm<NEXT_MIN>();
-        else
-          waitVm<0>();
-      } else {
+      if constexpr(!(DBG & 32))
         waitVm<0>();
-      }
       barrierKeepDma();
       request(chunk + R);
     }
     if constexpr(F8C) {
-      convertStep(st & 1);  // this step's fragments were read in the previous iteration
       if((st & 1) && !(DBG & 4))
         f8pair();  // steps st - 1 (low halves) and st (high halves)
     }
     if(chunkEnd && chunk + 1 < NCH && (DBG & 2) && !(DBG & 1))
       request(chunk + R);  // ablation: the requests without their waits / barriers
-    constexpr bool LATE = (F8C && KC_F8C_LATE) || (G::MODE == NN_MODE_SPLIT3 && G::BL && KC_ACC_LATE);
-    if(!LATE && st + 1 < STEPS && !(DBG & 16)) {
+    // (reading them after this step's MFMAs issue instead -- one fragment buffer -- spills
+    // less under the cap but ran the network 3 % slower: the measurements at KC_F8C_VGPR)
+    if(st + 1 < STEPS && !(DBG & 16)) {
       if(cb == NCB - 1)
         tapAddr(tap + 1);
       loadStep(st + 1, (st + 1) & 1);
@@ -720,13 +617,6 @@ KC_D void convTilesB(const uint16_t* __restrict__ act, const h16x8* __restrict__
 #pragma unroll
         for(int ct = 0; ct < G::NCT; ct++)
           acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[b][ct], afl[b][t], acc[t][ct], 0, 0, 0);
-    }
-    if(LATE && st + 1 < STEPS) {
-      // the next step's fragments, read once this step's MFMAs are issued
-      __builtin_amdgcn_sched_barrier(0);
-      if(cb == NCB - 1)
-        tapAddr(tap + 1);
-      loadStep(st + 1, (st + 1) & 1);
     }
     if constexpr(F8C) {
       if(st == STEPS - 1 && !(st & 1) && !(DBG & 4)) {
@@ -756,7 +646,7 @@ KC_D f32x4* trunkBase(float* trunk, int wave, int lane) {
 // parked trunk fits in 24 more registers (< 256, no spill): kept in `reg`, no scratch.
 template <class G>
 constexpr bool regTrunk() {
-  return G::MAXT * G::NCT <= 6 && !(G::MODE == NN_MODE_F8C && KC_F8C_PARK);
+  return G::MAXT * G::NCT <= 6;
 }
 template <class G>
 KC_D void storeTrunk(float* trunk, f32x4 (&reg)[G::MAXT][G::NCT], const f32x4 (&a)[G::MAXT][G::NCT], int wave,
@@ -839,8 +729,7 @@ KC_D void flagHot(int* hot, int base, int nb, int tstart, int lane, const float 
   }
 }
 // Four activated channels of one row into act: the hi plane, and the second plane --
-// fp16 lo (mode 1), or e4m3(lo(x) 2^11), one byte per channel (mode 2; e4m3(x) is
-// converted from the hi plane's fp16 value inside the convolution).
+// fp16 lo (mode 1), or the e4m3 pairs of hi(x) and lo(x) 2^11 (mode 2).
 template <class G>
 KC_D void storeAct4(uint16_t* act, int row, int ch, float y0, float y1, float y2, float y3) {
   *reinterpret_cast<uint2*>(act + row * G::ASTR + ch) = packH4(y0, y1, y2, y3);
@@ -848,27 +737,22 @@ KC_D void storeAct4(uint16_t* act, int row, int ch, float y0, float y1, float y2
     *reinterpret_cast<uint2*>(act + G::PLANE_BYTES / 2 + row * G::ASTR + ch) = packH4lo(y0, y1, y2, y3);
   if constexpr(G::MODE == NN_MODE_F8C) {
     auto lo = [](float x) { return (x - (float)(_Float16)x) * F8C_SCALE; };
-    if constexpr(G::F8X) {
-      *reinterpret_cast<int*>(reinterpret_cast<char*>(act) + G::PLANE_BYTES + row * G::ROWB2 + ch) =
-          e4m3x2<true>(lo(y2), lo(y3), e4m3x2<false>(lo(y0), lo(y1), 0));
-    } else {
-      // the channel octet's 16 bytes: [hi(x) of its 8 channels | lo(x) 2^11 of its 8 channels]
-      auto hi = [](float x) { return (float)(_Float16)x; };
-      char* q = reinterpret_cast<char*>(act) + G::PLANE_BYTES + row * G::ROWB + (ch >> 3) * 16 + (ch & 7);
-      *reinterpret_cast<int*>(q) = e4m3x2<true>(hi(y2), hi(y3), e4m3x2<false>(hi(y0), hi(y1), 0));
-      *reinterpret_cast<int*>(q + 8) = e4m3x2<true>(lo(y2), lo(y3), e4m3x2<false>(lo(y0), lo(y1), 0));
-    }
+    // the channel octet's 16 bytes: [hi(x) of its 8 channels | lo(x) 2^11 of its 8 channels]
+    auto hi = [](float x) { return (float)(_Float16)x; };
+    char* q = reinterpret_cast<char*>(act) + G::PLANE_BYTES + row * G::ROWB + (ch >> 3) * 16 + (ch & 7);
+    *reinterpret_cast<int*>(q) = e4m3x2<true>(hi(y2), hi(y3), e4m3x2<false>(hi(y0), hi(y1), 0));
+    *reinterpret_cast<int*>(q + 8) = e4m3x2<true>(lo(y2), lo(y3), e4m3x2<false>(lo(y0), lo(y1), 0));
   }
 }
 // BL: zero the shared zero row in every plane (after act was used as f32 scratch).
 template <class G>
 KC_D void zeroRowBL(uint16_t* act, int tid) {
-  constexpr int N = G::ROWB / 16, N2 = G::SPLIT ? G::ROWB2 / 16 : 0;
+  constexpr int N = G::ROWB / 16;
   char* a = reinterpret_cast<char*>(act);
   if(tid < N)
     reinterpret_cast<uint4*>(a + G::ZROW * G::ROWB)[tid] = uint4{0u, 0u, 0u, 0u};
-  else if(tid < N + N2)
-    reinterpret_cast<uint4*>(a + G::PLANE_BYTES + G::ZROW * G::ROWB2)[tid - N] = uint4{0u, 0u, 0u, 0u};
+  else if(tid < 2 * N)
+    reinterpret_cast<uint4*>(a + G::PLANE_BYTES + G::ZROW * G::ROWB)[tid - N] = uint4{0u, 0u, 0u, 0u};
 }
 
 // act[pad(row)][ch..ch+3] = f16(relu(v * s[ch] + b[ch])) for on-board rows, all channels.
@@ -1201,7 +1085,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
   const int tstart = rg * G::MAXT;
   uint16_t* act = reinterpret_cast<uint16_t*>(smem);
   float* actF = reinterpret_cast<float*>(smem);
-  float* scr = reinterpret_cast<float*>(smem + G::SCR_OFF);
+  float* scr = reinterpret_cast<float*>(smem + G::OFF_SCR);
   float* poolP = reinterpret_cast<float*>(smem + G::OFF_POOL);
   float* poolV = poolP + G::NB * 96;
   float* biasS = reinterpret_cast<float*>(smem + G::OFF_BIAS);
@@ -1219,11 +1103,8 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
     constexpr int CH0 = G::tapPieces(1);  // 1-KiB pieces per stem tap (one 32-channel block)
     const uint32_t ring = ldsAddr(wl);
     if constexpr(G::BL) {
-      // the stem's chunks 0 .. RING-2 into slots 0 .. RING-2 (its chunks are whole: 3 or 9 taps)
-      constexpr int SC = G::firstChunkPieces(1, 9);
-#pragma unroll
-      for(int j = 0; j + 1 < G::RING && j < G::chunks(1, 9); j++)
-        stageChunk<G::NW>(WB + L->wInit + (size_t)j * SC * 64, ring + j * G::WSLOT * 16, SC, wave, lane);
+      // the stem's chunk 0 (three taps) into slot 0
+      stageChunk<G::NW>(WB + L->wInit, ring, G::firstChunkPieces(1, 9), wave, lane);
     } else {
 #pragma unroll
       for(int tap = 0; tap < 2; tap++)
@@ -1263,7 +1144,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
           const int c = i / G::A, p = i - c * G::A;
           const int row = G::BL ? b * G::A + p : padCell<G>(b, p);
           act[row * G::ASTR + c] = (uint16_t)0x3c00;  // 1.0 (its lo planes stay 0)
-          if constexpr(G::MODE == NN_MODE_F8C && !G::F8X)  // e4m3 1.0 in the pair plane
+          if constexpr(G::MODE == NN_MODE_F8C)  // e4m3 1.0 in the pair plane
             reinterpret_cast<uint8_t*>(act)[G::PLANE_BYTES + row * G::ROWB + (c >> 3) * 16 + (c & 7)] = 0x38;
         }
       }
@@ -1334,14 +1215,11 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
       pre[j] = loadParam(L, WF, blk + 1, tid + j * G::NT);  // next slab: its latency hides behind conv1
     NN_PHASE(4 + 4 * blk);
     if constexpr(G::BL)
-      // first chunk mod RING: stem 3 chunks, each block's convs 9 + 9 (a 64-channel tap is one
-      // chunk too), so conv1 starts at 3 + 18 blk (1 mod 2, 0 mod 3) and conv2 at 12 + 18 blk (0)
-      convTilesB<G, 9, G::C / 32, G::RING == 2 ? 1 : 0>(act, WB + L->wConv1[blk], wl, acc, rb, vm, cg, lane, tid,
-                                                       WB + L->wConv2[blk],
-                                                       L->kinds[blk] == 0 ? G::firstChunkPieces(3, 9)
-                                                                          : G::firstChunkPieces(2, 9),
-                                                       L->kinds[blk] == 0 ? G::chunks(3, 9) : G::chunks(2, 9),
-                                                       L->sConv1[blk]);
+      // first chunk's parity: stem 3 chunks, each block's convs 9 + 9 (a 64-channel tap is one
+      // chunk too), so conv1 starts at 3 + 18 blk (odd) and conv2 at 12 + 18 blk (even)
+      convTilesB<G, 9, G::C / 32, 1>(act, WB + L->wConv1[blk], wl, acc, rb, vm, cg, lane, tid, WB + L->wConv2[blk],
+                                     L->kinds[blk] == 0 ? G::firstChunkPieces(3, 9) : G::firstChunkPieces(2, 9),
+                                     L->kinds[blk] == 0 ? G::chunks(3, 9) : G::chunks(2, 9), L->sConv1[blk]);
     else
       convTiles<G, 9, G::C / 32, 1, 0, false>(act, WB + L->wConv1[blk], wl, acc, ab, cg, lane, tid,
                                               WB + L->wConv2[blk],
@@ -1512,15 +1390,14 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
   // ---- heads: one 1x1 conv C -> [p1 | g1 | v1] ----
   zeroAcc<G>(acc);
   if constexpr(G::BL)
-    convTilesB<G, 1, G::C / 32, G::RING == 2 ? 1 : 0>(act, WB + L->wHead, wl, acc, rb, vm, cg, lane, tid, nullptr, 0,
-                                                      0, L->sHead);
+    convTilesB<G, 1, G::C / 32, 1>(act, WB + L->wHead, wl, acc, rb, vm, cg, lane, tid, nullptr, 0, 0, L->sHead);
   else
     convTiles<G, 1, G::C / 32, 1, 0, false>(act, WB + L->wHead, wl, acc, ab, cg, lane, tid, nullptr, 0, 0,
                                             9 + 18 * L->nblocks);
   __syncthreads();  // act dead from here: f32 [MROWS][SCR] value branch at actF, g branch at scr
   NN_PHASE(41);
   // the ring is idle too: the head linears' weights land in its front (published by the
-  // stage epilogue's barrier below; scr, where it is a ring slot, is slot 1)
+  // stage epilogue's barrier below)
   float* plgT = reinterpret_cast<float*>(wl);
   float* l2T = plgT + 32 * 96;
   // the head slab, in the idle parameter slab: value / misc output weights [4][v2], their
@@ -1648,7 +1525,7 @@ __global__ void __launch_bounds__(512, 2) KC_NN_KERNEL_ATTR
 
 #ifndef KC_NN_KERNEL_ONLY
 #if KC_F8C_VGPR
-// the register-capped corrected instance (nn_corr.hip)
+// the register-capped borderless instances (nn_corr.hip)
 template <int X, int Y, int C, int NB, int MODE, bool BL>
 __global__ void kNNForwardCap(const NNLayout* __restrict__ L, const h16x8* __restrict__ WB,
                               const float* __restrict__ WF, const uint16_t* __restrict__ tabs, int n,
@@ -1659,8 +1536,8 @@ __global__ void kNNForwardCap(const NNLayout* __restrict__ L, const h16x8* __res
 template <class G>
 constexpr auto nnKernel() {
 #if KC_F8C_VGPR
-  if constexpr(G::MODE == NN_MODE_F8C || (G::MODE == NN_MODE_F16 && G::BL) ||
-               (KC_ACC_CAP && G::MODE == NN_MODE_SPLIT3 && G::BL))
+  // the borderless instances: corrected, and accurate (split)
+  if constexpr(G::BL)
     return kNNForwardCap<G::X, G::Y, G::C, G::NB, G::MODE, G::BL>;
   else
 #endif
@@ -1733,10 +1610,10 @@ static uint8_t f2e4m3(float f) {
 }
 
 // mode 1: after each tap's hi fragments the same fragments of lo = fp16(w - hi);
-// mode 2: after them e4m3(lo(w) 2^(11-sw)) of each fragment's 8 k, 8 bytes per lane (512 B
-// per fragment; e4m3(hi(w) 2^-sw) is converted from the hi fragment on the device), sw the
-// conv's block exponent (f8Exp of its largest |w|), and *sA = the A operand's E8M0 scale
-// byte, 127 - 11 + sw (convTiles' / convTilesB's SPLIT ring slot layout).
+// mode 2: after them, per fragment and lane, the 16 bytes [e4m3(lo(w) 2^(11-sw)) |
+// e4m3(hi(w) 2^-sw)] of the fragment's 8 k, sw the conv's block exponent (f8Exp of its
+// largest |w|), and *sA = the A operand's E8M0 scale byte, 127 - 11 + sw (convTiles' /
+// convTilesB's SPLIT ring slot layout).
 static void packConv(std::vector<uint16_t>& dst, int ntaps, int cinPad, int cout,
                      const std::function<float(int, int, int)>& W, int mode = NN_MODE_F16, int* sA = nullptr) {
   const int ncb = cinPad / 32, nct = cout / 16;
@@ -1764,12 +1641,6 @@ static void packConv(std::vector<uint16_t>& dst, int ntaps, int cinPad, int cout
                 const uint16_t hi = f2h(w[j]);
                 dst.push_back(part == 0 ? hi : f2h(w[j] - h2f(hi)));
               }
-            } else if(KC_F8C_CVTW) {
-              uint8_t b[8];
-              for(int j = 0; j < 8; j++)
-                b[j] = f2e4m3(ldexpf((w[j] - h2f(f2h(w[j]))) * F8C_SCALE, -sw));
-              for(int j = 0; j < 4; j++)
-                dst.push_back((uint16_t)(b[2 * j] | (b[2 * j + 1] << 8)));
             } else {
               uint8_t b[16];
               for(int j = 0; j < 8; j++) {
@@ -2092,17 +1963,8 @@ void NNEngine::build(const ModelHost& m, int path) {
                              G4::LDS));
   KC_HIP(hipFuncSetAttribute((const void*)kNNForward<5, 5, 96, 2, NN_MODE_SPLIT3, false>,
                              hipFuncAttributeMaxDynamicSharedMemorySize, GS::LDS));
-  KC_HIP(hipFuncSetAttribute((const void*)kNNForward<5, 5, 96, NN_SMALL_NB, NN_MODE_SPLIT3, true>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, GB::LDS));
+  KC_HIP(hipFuncSetAttribute((const void*)nnKernel<GB>(), hipFuncAttributeMaxDynamicSharedMemorySize, GB::LDS));
   KC_HIP(hipFuncSetAttribute((const void*)nnKernel<GC>(), hipFuncAttributeMaxDynamicSharedMemorySize, GC::LDS));
-  using GF = NNGeo<5, 5, 96, NN_SMALL_NB, 0, true>;
-  KC_HIP(hipFuncSetAttribute((const void*)nnKernel<GF>(), hipFuncAttributeMaxDynamicSharedMemorySize, GF::LDS));
-#ifdef KC_AB_HOOKS
-  // A/B builds only (tools/Makefile alt, -DKC_AB_HOOKS): KATACOFFEE_NN_SMALL=8 runs small
-  // batches on the 8-board instance too; the product library never reads the variable
-  const char* small = getenv("KATACOFFEE_NN_SMALL");
-  small_ = small ? atoi(small) : 0;
-#endif
   int dev = 0;
   KC_HIP(hipGetDevice(&dev));
   KC_HIP(hipDeviceGetAttribute(&cus_, hipDeviceAttributeMultiprocessorCount, dev));
@@ -2166,29 +2028,16 @@ void NNEngine::forward(int n, const uint64_t* in, float* out, hipStream_t st, co
       KC_HIP(hipMemsetAsync(hot_, 0, (size_t)grid * NN_SMALL_NB * 4, st));
       hotCap_ = grid * NN_SMALL_NB;
     }
-#ifdef KC_AB_NO_FALLBACK
-    launch<NNGeo<5, 5, 96, NN_SMALL_NB, NN_MODE_F8C, true>>(n, inWords, tabDevB_, in, out, st, countDev, rowIdx, e0, e1,
-                                                            hot_);
-#else
     launch<NNGeo<5, 5, 96, NN_SMALL_NB, NN_MODE_F8C, true>>(n, inWords, tabDevB_, in, out, st, countDev, rowIdx, e0,
                                                             fallback_ ? nullptr : e1, hot_);
-#endif
-#ifdef KC_AB_NO_FALLBACK  // A/B builds: the cost of the (empty) re-evaluation launch
-    if(false)
-#else
     if(fallback_)  // the accurate engine's split weights, this engine's flags
-#endif
       fallbackNet_->launch<NNGeo<5, 5, 96, NN_SMALL_NB, NN_MODE_SPLIT3, true>>(
           n, inWords, fallbackNet_->tabDevB_, in, out, st, countDev, rowIdx, nullptr, e1, hot_);
   }
   else if(mode_ == NN_ACCURATE_NB2)
     launch<NNGeo<5, 5, 96, 2, NN_MODE_SPLIT3, false>>(n, inWords, tabDevS_, in, out, st, countDev, rowIdx, e0, e1);
-  else if(n <= NN_SMALL_NB * cus_ && small_ != 8) {
-    if(KC_FAST_BL)
-      launch<NNGeo<5, 5, 96, NN_SMALL_NB, 0, true>>(n, inWords, tabDevB_, in, out, st, countDev, rowIdx, e0, e1);
-    else
-      launch<NNGeo<5, 5, 96, NN_SMALL_NB, 0>>(n, inWords, tabDevSm_, in, out, st, countDev, rowIdx, e0, e1);
-  }
+  else if(n <= NN_SMALL_NB * cus_)
+    launch<NNGeo<5, 5, 96, NN_SMALL_NB, 0>>(n, inWords, tabDevSm_, in, out, st, countDev, rowIdx, e0, e1);
   else
     launch<NNGeo<5, 5, 96, 8, 0>>(n, inWords, tabDev_, in, out, st, countDev, rowIdx, e0, e1);
 }

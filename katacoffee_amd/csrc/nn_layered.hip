@@ -264,19 +264,6 @@ __device__ unsigned long long g_convlProf[8];
   } while(0)
 #endif
 
-// Same-box A/B switches (tools/build_variant.sh): KC_CONVL_LATE_PRO 1 requests the first
-// slice and weights after the prologue's barrier, KC_CONVL_LATE_STORE 1 runs the next
-// slice's prologue after the last tap (both: the round-5 kernel); KC_CONVL_STORE_TAP the
-// tap before which it runs otherwise
-#ifndef KC_CONVL_LATE_PRO
-#define KC_CONVL_LATE_PRO 0
-#endif
-#ifndef KC_CONVL_LATE_STORE
-#define KC_CONVL_LATE_STORE 0
-#endif
-#ifndef KC_CONVL_STORE_TAP
-#define KC_CONVL_STORE_TAP 5
-#endif
 template <int X, int Y, int KT, int TN, bool SPLIT, int WN>
 __global__ void __launch_bounds__(L_NT, 2) kConvL(LConvArgs a) {
   using G = LGeo<X, Y>;
@@ -317,7 +304,6 @@ __global__ void __launch_bounds__(L_NT, 2) kConvL(LConvArgs a) {
   };
   const int S = NCB * T;
   StageRegs<G> sr;
-#if !KC_CONVL_LATE_PRO
   // the first slice's activations and the first K steps' weights are requested before the
   // LDS clear and the parameter copy, so their latency overlaps them (round 5 issued them
   // after that barrier: 10.2 k of the split conv's 100.9 k cycles per workgroup were its
@@ -327,7 +313,6 @@ __global__ void __launch_bounds__(L_NT, 2) kConvL(LConvArgs a) {
   for(int i = 0; i < R - 1; i++)
     if(i < S)
       loadB(i, i);
-#endif
   // zero both stages (borders and boards past the batch stay zero), parameters to LDS
   for(int i = tid; i < 2 * PLANES * G::stage(SPLIT) / 16; i += L_NT)
     reinterpret_cast<uint4*>(smem)[i] = uint4{0u, 0u, 0u, 0u};
@@ -340,9 +325,6 @@ __global__ void __launch_bounds__(L_NT, 2) kConvL(LConvArgs a) {
     for(int i = tid; i < nb * a.gbLd; i += L_NT)
       sG[i] = a.gb[(size_t)base * a.gbLd + i];
   __syncthreads();
-#if KC_CONVL_LATE_PRO
-  stageLoad<G>(a, sr, 0, base, nb, tid);
-#endif
   stageStore<G, SPLIT>(a, sr, stage, stage + G::stage(SPLIT), 0, base, nb, sS, sB, sG, tid);
 
   // per-lane A row bases (bytes, shifted to the (-r,-r) neighbour), padding rows -> row 0
@@ -364,12 +346,6 @@ __global__ void __launch_bounds__(L_NT, 2) kConvL(LConvArgs a) {
     for(int c = 0; c < TN; c++)
       acc[t][c] = lf32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
-#if KC_CONVL_LATE_PRO
-#pragma unroll
-  for(int i = 0; i < R - 1; i++)
-    if(i < S)
-      loadB(i, i);
-#endif
   __syncthreads();
 
   // one K step: tap of slice cb from the stage at stHi/stLo, B slot `slot`
@@ -405,10 +381,10 @@ __global__ void __launch_bounds__(L_NT, 2) kConvL(LConvArgs a) {
     if(cb + 1 < NCB)
       stageLoad<G>(a, sr, cb + 1, base, nb, tid);
     // the next slice's prologue (BN-ReLU, hi/lo split, LDS stores into the other stage,
-    // which no wave reads during this slice) runs between this slice's taps STORE_TAP - 1
-    // and STORE_TAP, so its VALU work and LDS writes overlap the MFMAs in flight instead
-    // of running after them (round 5: after the last tap, 9.1 k cycles per workgroup)
-    constexpr int STORE_TAP = KC_CONVL_LATE_STORE ? T : (T % 3 == 0 ? KC_CONVL_STORE_TAP : T);
+    // which no wave reads during this slice) runs between this slice's taps 4 and 5 (3x3;
+    // 1x1: after its one tap), so its VALU work and LDS writes overlap the MFMAs in flight
+    // instead of running after them (round 5: after the last tap, 9.1 k cycles per workgroup)
+    constexpr int STORE_TAP = T % 3 == 0 ? 5 : T;
     auto storeNext = [&]() {
       if(cb + 1 < NCB) {
         char* nHi = stage + ((cb + 1) & 1) * PLANES * G::stage(SPLIT);
@@ -751,30 +727,29 @@ __global__ void __launch_bounds__(L_NT, 2) kConv1L(LConvArgs a) {
   convEpilogue<G, TM, TN>(a, acc, base, nb, wm, ctBase, lane);
 }
 
-// 1x1 convolutions, pipelined: 64-channel stages, double-buffered in LDS; the next stage's
-// global loads are issued before the current stage's MFMAs and converted (BN-ReLU -> fp16,
-// and for SPLIT the lo = x - fp16(x) plane) into the other buffer after them, so the HBM
-// latency of the f32 input overlaps the MFMAs (kConv1L waits for each stage before any
-// MFMA: 5 % MFMA busy on b18c384nbt's bottleneck convs).  Rows are 40 dwords (64 channels +
-// 16 pad: 10 mod 16 chunks, conflict-free A-fragment reads for contiguous rows).  SPLIT
-// (round 6): a stage holds a hi and a lo plane, each K step issues
-// hi*hi, lo(w)*hi(x), hi(w)*lo(x) -- kConv1L's products in kConv1L's order (an A/B
-// option: see kConv1PipeFor).
+// 1x1 convolutions of the fast path, pipelined: 64-channel stages, double-buffered in LDS;
+// the next stage's global loads are issued before the current stage's MFMAs and converted
+// (BN-ReLU -> fp16) into the other buffer after them, so the HBM latency of the f32 input
+// overlaps the MFMAs (kConv1L waits for each stage before any MFMA: 5 % MFMA busy on
+// b18c384nbt's bottleneck convs).  Rows are 40 dwords (64 channels + 16 pad: 10 mod 16
+// chunks, conflict-free A-fragment reads for contiguous rows).  The split path's 1x1 convs
+// run kConv1L: a split instance of this kernel (a hi and a lo plane per stage) was correct
+// but measured equal in round 6 (b18c384nbt accurate 54.95 vs 54.99 ms, b10c128
+// 1.99-2.02 ms either way, profiles/r06/split_1x1_pipe_ab.txt).
 constexpr int L1P_SW = 2;                  // 32-channel slices per stage
 constexpr int L1P_STRIDE = 32 * L1P_SW + 16;  // fp16 per staged row
 
-template <int X, int Y, bool SPLIT>
+template <int X, int Y>
 constexpr size_t l1pLds(int cin) {
-  return 2 * (SPLIT ? 2 : 1) * (size_t)LGeo<X, Y>::ROWS * L1P_STRIDE * 2 + 2 * (size_t)cin * 4;
+  return 2 * (size_t)LGeo<X, Y>::ROWS * L1P_STRIDE * 2 + 2 * (size_t)cin * 4;
 }
 
-template <int X, int Y, int TN, bool SPLIT, int WN>
+template <int X, int Y, int TN, int WN>
 __global__ void __launch_bounds__(L_NT, 2) kConv1LP(LConvArgs a) {
   using G = LGeo<X, Y>;
   constexpr int WM = L_WAVES / WN, TM = (G::RT + WM - 1) / WM;
   constexpr int NCT = TN * WN;
-  constexpr int SB = G::ROWS * L1P_STRIDE * 2;  // one plane of one stage buffer
-  constexpr int PL = SPLIT ? 2 : 1;
+  constexpr int SB = G::ROWS * L1P_STRIDE * 2;  // one stage buffer
   constexpr int CPR = 4 * L1P_SW;           // 8-channel chunks per staged row
   constexpr int TASKS = G::ROWS * CPR;
   constexpr int TPT = (TASKS + L_NT - 1) / L_NT;
@@ -787,7 +762,7 @@ __global__ void __launch_bounds__(L_NT, 2) kConv1LP(LConvArgs a) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave / WN, wn = wave % WN;
   const int ctBase = blockIdx.y * NCT + wn * TN;
-  float* sS = reinterpret_cast<float*>(smem + 2 * PL * SB);
+  float* sS = reinterpret_cast<float*>(smem + 2 * SB);
   float* sB = sS + a.cin;
   for(int i = tid; i < a.cin; i += L_NT) {
     sS[i] = i < a.cinReal ? a.ps[i] : 0.0f;
@@ -829,18 +804,6 @@ __global__ void __launch_bounds__(L_NT, 2) kConv1LP(LConvArgs a) {
       hi.z = packHalf2(v[4], v[5]);
       hi.w = packHalf2(v[6], v[7]);
       *reinterpret_cast<uint4*>(buf + (r * L1P_STRIDE + q * 8) * 2) = hi;
-      if constexpr(SPLIT) {
-        float lo[8];
-#pragma unroll
-        for(int j = 0; j < 8; j++)
-          lo[j] = v[j] - (float)(_Float16)v[j];
-        uint4 l4;
-        l4.x = packHalf2(lo[0], lo[1]);
-        l4.y = packHalf2(lo[2], lo[3]);
-        l4.z = packHalf2(lo[4], lo[5]);
-        l4.w = packHalf2(lo[6], lo[7]);
-        *reinterpret_cast<uint4*>(buf + SB + (r * L1P_STRIDE + q * 8) * 2) = l4;
-      }
     }
   };
   int ab[TM];
@@ -858,16 +821,12 @@ __global__ void __launch_bounds__(L_NT, 2) kConv1LP(LConvArgs a) {
     for(int c = 0; c < TN; c++)
       acc[t][c] = lf32x4{0.0f, 0.0f, 0.0f, 0.0f};
   const lh16x8* wl = a.w + (size_t)ctBase * 64 + lane;
-  const lh16x8* wlo = SPLIT ? a.wlo + (size_t)ctBase * 64 + lane : nullptr;
   const size_t stepStride = (size_t)a.coutTiles * 64;
-  lh16x8 bh[2][TN], bl[2][SPLIT ? TN : 1];
+  lh16x8 bh[2][TN];
   auto loadB = [&](int s, int slot) {
 #pragma unroll
-    for(int c = 0; c < TN; c++) {
+    for(int c = 0; c < TN; c++)
       bh[slot][c] = wl[(size_t)s * stepStride + c * 64];
-      if constexpr(SPLIT)
-        bl[slot][c] = wlo[(size_t)s * stepStride + c * 64];
-    }
   };
   load(0);
   loadB(0, 0);
@@ -875,7 +834,7 @@ __global__ void __launch_bounds__(L_NT, 2) kConv1LP(LConvArgs a) {
   store(0, smem);
   __syncthreads();
   for(int st = 0; st < NST; st++) {
-    const char* cur = smem + (st & 1) * PL * SB;
+    const char* cur = smem + (st & 1) * SB;
     if(st + 1 < NST)
       load(st + 1);
 #pragma unroll
@@ -885,26 +844,18 @@ __global__ void __launch_bounds__(L_NT, 2) kConv1LP(LConvArgs a) {
         break;
       if(s + 1 < NCB)
         loadB(s + 1, (j + 1) & 1);
-      lh16x8 ah[TM], al[SPLIT ? TM : 1];
+      lh16x8 ah[TM];
 #pragma unroll
-      for(int t = 0; t < TM; t++) {
+      for(int t = 0; t < TM; t++)
         ah[t] = *reinterpret_cast<const lh16x8*>(cur + ab[t] + 64 * j);
-        if constexpr(SPLIT)
-          al[t] = *reinterpret_cast<const lh16x8*>(cur + SB + ab[t] + 64 * j);
-      }
 #pragma unroll
       for(int t = 0; t < TM; t++)
 #pragma unroll
-        for(int c = 0; c < TN; c++) {
+        for(int c = 0; c < TN; c++)
           acc[t][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j & 1][c], ah[t], acc[t][c], 0, 0, 0);
-          if constexpr(SPLIT) {
-            acc[t][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bl[j & 1][c], ah[t], acc[t][c], 0, 0, 0);
-            acc[t][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bh[j & 1][c], al[t], acc[t][c], 0, 0, 0);
-          }
-        }
     }
     if(st + 1 < NST)
-      store(st + 1, smem + ((st + 1) & 1) * PL * SB);
+      store(st + 1, smem + ((st + 1) & 1) * SB);
     __syncthreads();
   }
   convEpilogue<G, TM, TN>(a, acc, base, nb, wm, ctBase, lane);
@@ -1059,26 +1010,11 @@ uint16_t lf2h(float f) {
   return u;
 }
 
-#ifdef KC_NO_LDSB  // (A/B builds)
-constexpr bool kConvLdsB = false;
-#else
-constexpr bool kConvLdsB = true;
-#endif
-// the fast path's 1x1 convs always run the pipelined kernel; the split path's run kConv1L
-// unless built with -DKC_SPLIT_1X1_PIPE (round 6: the pipelined split instance is correct --
-// test_gpu_nn / test_gpu_train green -- but measured equal: b18c384nbt accurate 54.95 vs
-// 54.99 ms, b10c128 1.99-2.02 ms either way, profiles/r06/split_1x1_pipe_ab.txt)
-#ifdef KC_SPLIT_1X1_PIPE
-template <bool SPLIT>
-constexpr bool kConv1PipeFor = true;
-#else
-template <bool SPLIT>
-constexpr bool kConv1PipeFor = !SPLIT;
-#endif
-
 constexpr size_t L_LDS_BUDGET = 160 * 1024;
 
-// Dynamic LDS of a conv's launch, and whether a 1x1 takes the pipelined kernel.  The
+// Dynamic LDS of a conv's launch, and whether a 1x1 takes the pipelined kernel (the fast
+// path's, where its stages fit; the split path's run kConv1L).  Fast 3x3 convs on the 4 x 2
+// wave grid take kConvLB (weights through LDS), every other 3x3 kConvL.  The
 // constructor evaluates it for every conv of the net, so a net too wide for the budget is
 // refused there and not in the middle of a forward.
 template <int X, int Y>
@@ -1087,14 +1023,13 @@ size_t convLds(int kt, int tn, int wn, bool split, int cin, int gbLd, bool* pipe
   const size_t prm = (2 * (size_t)cin + (size_t)G::BPW * (gbLd > 0 ? gbLd : 0)) * 4;
   *pipe = false;
   if(kt == 1) {
-    const size_t lp = split ? l1pLds<X, Y, true>(cin) : l1pLds<X, Y, false>(cin);
-    if((split ? kConv1PipeFor<true> : kConv1PipeFor<false>) && lp <= L_LDS_BUDGET) {
+    if(!split && l1pLds<X, Y>(cin) <= L_LDS_BUDGET) {
       *pipe = true;
-      return lp;
+      return l1pLds<X, Y>(cin);
     }
     return (split ? 2 * (size_t)l1StageBytes<G, true>() : (size_t)l1StageBytes<G, false>()) + 2 * (size_t)cin * 4;
   }
-  if(kConvLdsB && !split && wn == 2)
+  if(!split && wn == 2)
     return 2 * (size_t)G::stage(false) + 2 * 3 * (size_t)tn * wn * 1024 + prm;
   return 2 * (split ? 2 : 1) * (size_t)G::stage(split) + prm;
 }
@@ -1108,17 +1043,20 @@ size_t convLdsAt(int X, int kt, int tn, int wn, bool split, int cin, int gbLd) {
 
 template <int X, int Y, int KT, int TN, bool SPLIT, int WN>
 void launchConvT(const LConvArgs& a, int grid, hipStream_t st) {
-  const void* fnp;
+  void (*kern)(LConvArgs);
   bool pipe;
   const size_t lds = convLds<X, Y>(KT, TN, WN, SPLIT, a.cin, a.gbLd, &pipe);
   if constexpr(KT == 1) {
     if(a.pro != PRO_BN)
       throw std::invalid_argument("1x1 convolutions take a BN-ReLU prologue");
-    fnp = pipe ? (const void*)kConv1LP<X, Y, TN, SPLIT, WN> : (const void*)kConv1L<X, Y, TN, SPLIT, WN>;
-  } else if constexpr(kConvLdsB && !SPLIT && WN == 2) {
-    fnp = (const void*)kConvLB<X, Y, TN, WN>;
+    kern = kConv1L<X, Y, TN, SPLIT, WN>;
+    if constexpr(!SPLIT)
+      if(pipe)
+        kern = kConv1LP<X, Y, TN, WN>;
+  } else if constexpr(!SPLIT && WN == 2) {
+    kern = kConvLB<X, Y, TN, WN>;
   } else {
-    fnp = (const void*)kConvL<X, Y, KT, TN, SPLIT, WN>;
+    kern = kConvL<X, Y, KT, TN, SPLIT, WN>;
   }
   if(lds > L_LDS_BUDGET)
     throw std::invalid_argument("layered conv: LDS budget exceeded");
@@ -1130,22 +1068,13 @@ void launchConvT(const LConvArgs& a, int grid, hipStream_t st) {
   KC_HIP(hipGetDevice(&dev));
   {
     std::lock_guard<std::mutex> lk(mu);
-    if(!done.count({dev, fnp})) {
-      KC_HIP(hipFuncSetAttribute(fnp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L_LDS_BUDGET));
-      done.insert({dev, fnp});
+    if(!done.count({dev, (const void*)kern})) {
+      KC_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L_LDS_BUDGET));
+      done.insert({dev, (const void*)kern});
     }
   }
   const int gy = (a.coutTiles + TN * WN - 1) / (TN * WN);
-  if constexpr(KT == 1) {
-    if(fnp == (const void*)kConv1LP<X, Y, TN, SPLIT, WN>)
-      hipLaunchKernelGGL((kConv1LP<X, Y, TN, SPLIT, WN>), dim3(grid, gy), dim3(L_NT), lds, st, a);
-    else
-      hipLaunchKernelGGL((kConv1L<X, Y, TN, SPLIT, WN>), dim3(grid, gy), dim3(L_NT), lds, st, a);
-  }
-  else if constexpr(kConvLdsB && !SPLIT && WN == 2)
-    hipLaunchKernelGGL((kConvLB<X, Y, TN, WN>), dim3(grid, gy), dim3(L_NT), lds, st, a);
-  else
-    hipLaunchKernelGGL((kConvL<X, Y, KT, TN, SPLIT, WN>), dim3(grid, gy), dim3(L_NT), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3(grid, gy), dim3(L_NT), lds, st, a);
   KC_HIP(hipGetLastError());
 }
 
@@ -1195,7 +1124,6 @@ static void chooseGrid(int cout, bool split, int& tn, int& wn) {
   wn = 2;
   tn = cout % 128 == 0 ? 4 : cout % 96 == 0 ? 3 : 2;
   const int gy2 = (tiles + 2 * tn - 1) / (2 * tn);
-#ifndef KC_LAYERED_WN2  // (A/B builds: csrc/Makefile `alt` target, ALT_FLAGS=-DKC_LAYERED_WN2)
   if(split)
     return;
   for(int t : {3, 2})
@@ -1204,10 +1132,6 @@ static void chooseGrid(int cout, bool split, int& tn, int& wn) {
       wn = 4;
       return;
     }
-#else
-  (void)split;
-  (void)gy2;
-#endif
 }
 
 NNLayered::NNLayered(const ModelHost& m, int X, int Y, int W, bool split)

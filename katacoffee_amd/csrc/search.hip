@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "detmath.h"
 #include "engine.h"
 #include "kc_board.h"
@@ -2092,16 +2094,13 @@ __global__ void __launch_bounds__(64, NI <= 4 ? 4 : 3) kBackup(const SearchDev* 
 // the NN cache, is handled by the tags (backupBody / cacheLookup / kResolve), so every
 // result is the one the two separate kernels give.  One kernel boundary less per round,
 // and a game's slow backup and slow descent no longer each set a kernel's length.
-// waves per SIMD the fused kernel is compiled for at 5x5 (A/B switch: 4 = 128 VGPRs, as
-// kSelect / kBackup; beside a network workgroup's two waves a SIMD holds one such wave.
+// At 5x5 the fused kernel is compiled for 4 waves per SIMD (128 VGPRs, as kSelect /
+// kBackup; beside a network workgroup's two waves a SIMD holds one such wave.
 // 6 (80 VGPRs: two fit) spills 332 B per lane and ran 18.0 k against 24.4 k rows/s, 5
 // 21.6 k: profiles/r05/fused_occupancy_ab.txt)
-#ifndef KC_FUSED_OCC
-#define KC_FUSED_OCC 4
-#endif
 template <int NI, bool EXPL = false>
-__global__ void __launch_bounds__(64, NI <= 2 ? KC_FUSED_OCC : 2) kBackupSelect(const SearchDev* __restrict__ dp,
-                                                                      const DTables* __restrict__ Tp) {
+__global__ void __launch_bounds__(64, NI <= 2 ? 4 : 2) kBackupSelect(const SearchDev* __restrict__ dp,
+                                                                     const DTables* __restrict__ Tp) {
   const SearchDev& d = *uniformConst(dp);  // constant views: see kBackup
   const DTables& T = *uniformConst(Tp);
   const int g = blockIdx.x;
@@ -4803,6 +4802,26 @@ __global__ void __launch_bounds__(64) kAnalysisReport(const SearchDev* __restric
 // ---------------------------------------------------------------------------
 static int laneItems(int P) { return P <= 128 ? 2 : (P <= 256 ? 4 : 7); }
 
+// The launchers' choice of a kernel instantiation: f is a generic lambda that takes the
+// choice as a type and names the kernel once -- byItems the engine's items per lane
+// (f(std::integral_constant<int, NI>{}), NI = laneItems(P)), byFlag a template flag
+// (f(std::true_type{}) or f(std::false_type{})).
+template <class F>
+static void byItems(int P, F f) {
+  switch(laneItems(P)) {
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 7>{}); break;
+  }
+}
+template <class F>
+static void byFlag(bool b, F f) {
+  if(b)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
 // ---------------------------------------------------------------------------
 // Row staging for device-resident gathers (coffee_selfplay_stage_rows): one wave per
 // row packs the row's six arrays into one contiguous record (rows.py FIELDS: bin u8
@@ -4851,13 +4870,9 @@ void launchStartPosCheck(const DTables* T, int P, const coffee_start_position* s
                          int32_t* info, hipStream_t st) {
   if(n <= 0)
     return;
-  const int ni = laneItems(P);
-  if(ni == 2)
-    hipLaunchKernelGGL((kStartPosCheck<2>), dim3(n), dim3(64), 0, st, T, samples, n, status, info);
-  else if(ni == 4)
-    hipLaunchKernelGGL((kStartPosCheck<4>), dim3(n), dim3(64), 0, st, T, samples, n, status, info);
-  else
-    hipLaunchKernelGGL((kStartPosCheck<7>), dim3(n), dim3(64), 0, st, T, samples, n, status, info);
+  byItems(P, [&](auto ni) {
+    hipLaunchKernelGGL(kStartPosCheck<ni()>, dim3(n), dim3(64), 0, st, T, samples, n, status, info);
+  });
   KC_HIP(hipGetLastError());
 }
 
@@ -4886,11 +4901,7 @@ void launchCompact(const SearchDev& d, const SearchDev* dd, hipStream_t st, bool
   else if(!resolve)
     hipLaunchKernelGGL((kCompact<2, false>), dim3(1), dim3(nt), 0, st, dd, T, a);
   else
-    switch(laneItems(d.P)) {
-      case 2: hipLaunchKernelGGL((kCompact<2, true>), dim3(1), dim3(nt), 0, st, dd, T, a); break;
-      case 4: hipLaunchKernelGGL((kCompact<4, true>), dim3(1), dim3(nt), 0, st, dd, T, a); break;
-      default: hipLaunchKernelGGL((kCompact<7, true>), dim3(1), dim3(nt), 0, st, dd, T, a); break;
-    }
+    byItems(d.P, [&](auto ni) { hipLaunchKernelGGL((kCompact<ni(), true>), dim3(1), dim3(nt), 0, st, dd, T, a); });
   KC_HIP(hipGetLastError());
 }
 
@@ -4911,98 +4922,41 @@ static bool explLaunch(const SearchDev& d) {
   return explOn(d.ex) || explOn(d.ex1) || rootSearchOn(d.rs) || rootSearchOn(d.rs1);
 }
 
-// KERNEL<NI, ...> by the engine's items per lane.
-#define KC_BY_ITEMS(LAUNCH, KERNEL, ...)                         \
-  switch(laneItems(d.P)) {                                       \
-    case 2: LAUNCH((KERNEL<2, __VA_ARGS__>)); break;             \
-    case 4: LAUNCH((KERNEL<4, __VA_ARGS__>)); break;             \
-    default: LAUNCH((KERNEL<7, __VA_ARGS__>)); break;            \
-  }
-
 void launchSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEvent_t e0, hipEvent_t e1,
                   bool resetCommit) {
-  const DTables* T = d.T;
   const int rc = resetCommit ? 1 : 0;
-#define KC_L(K) launchEv(K, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc)
-  if(explLaunch(d)) {
-    if(d.matchMode) {
-      KC_BY_ITEMS(KC_L, kSelect, true, true)
-    } else {
-      KC_BY_ITEMS(KC_L, kSelect, false, true)
-    }
-    KC_HIP(hipGetLastError());
-    return;
-  }
-#undef KC_L
-  if(d.matchMode) {
-    switch(laneItems(d.P)) {
-      case 2: launchEv(kSelect<2, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
-      case 4: launchEv(kSelect<4, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
-      default: launchEv(kSelect<7, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
-    }
-    KC_HIP(hipGetLastError());
-    return;
-  }
-  switch(laneItems(d.P)) {
-    case 2: launchEv(kSelect<2>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
-    case 4: launchEv(kSelect<4>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
-    default: launchEv(kSelect<7>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T, rc); break;
-  }
+  byItems(d.P, [&](auto ni) {
+    byFlag(d.matchMode, [&](auto m) {
+      byFlag(explLaunch(d), [&](auto e) {
+        launchEv(kSelect<ni(), m(), e()>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, d.T, rc);
+      });
+    });
+  });
   KC_HIP(hipGetLastError());
 }
 
 void launchBackup(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-  const DTables* T = d.T;
-#define KC_L(K) launchEv(K, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T)
-  if(explLaunch(d)) {
-    if(d.matchMode) {
-      KC_BY_ITEMS(KC_L, kBackup, true, true)
-    } else {
-      KC_BY_ITEMS(KC_L, kBackup, false, true)
-    }
-    KC_HIP(hipGetLastError());
-    return;
-  }
-  if(d.matchMode) {
-    switch(laneItems(d.P)) {
-      case 2: launchEv(kBackup<2, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
-      case 4: launchEv(kBackup<4, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
-      default: launchEv(kBackup<7, true>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
-    }
-    KC_HIP(hipGetLastError());
-    return;
-  }
-  switch(laneItems(d.P)) {
-    case 2: launchEv(kBackup<2>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
-    case 4: launchEv(kBackup<4>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
-    default: launchEv(kBackup<7>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
-  }
+  byItems(d.P, [&](auto ni) {
+    byFlag(d.matchMode, [&](auto m) {
+      byFlag(explLaunch(d), [&](auto e) {
+        launchEv(kBackup<ni(), m(), e()>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, d.T);
+      });
+    });
+  });
   KC_HIP(hipGetLastError());
 }
 
 void launchBackupSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-  const DTables* T = d.T;
-  if(explLaunch(d)) {
-    KC_BY_ITEMS(KC_L, kBackupSelect, true)
-    KC_HIP(hipGetLastError());
-    return;
-  }
-#undef KC_L
-  switch(laneItems(d.P)) {
-    case 2: launchEv(kBackupSelect<2>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
-    case 4: launchEv(kBackupSelect<4>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
-    default: launchEv(kBackupSelect<7>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, T); break;
-  }
+  byItems(d.P, [&](auto ni) {
+    byFlag(explLaunch(d), [&](auto e) {
+      launchEv(kBackupSelect<ni(), e()>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, d.T);
+    });
+  });
   KC_HIP(hipGetLastError());
 }
 
 void launchResolve(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
-  const DTables* T = d.T;
-  switch(laneItems(d.P)) {
-    case 2: hipLaunchKernelGGL(kResolve<2>, dim3(RESOLVE_GRID), dim3(64), 0, st, dd, T); break;
-    case 4: hipLaunchKernelGGL(kResolve<4>, dim3(RESOLVE_GRID), dim3(64), 0, st, dd, T); break;
-    default: hipLaunchKernelGGL(kResolve<7>, dim3(RESOLVE_GRID), dim3(64), 0, st, dd, T); break;
-  }
+  byItems(d.P, [&](auto ni) { hipLaunchKernelGGL(kResolve<ni()>, dim3(RESOLVE_GRID), dim3(64), 0, st, dd, d.T); });
   KC_HIP(hipGetLastError());
 }
 
@@ -5012,68 +4966,28 @@ void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
     // the idle slots take the queries submitted so far
     hipLaunchKernelGGL(kAnalysisSubmitted, dim3(1), dim3(1), 0, st, dd, d.aSubmitted);
     KC_HIP(hipGetLastError());
-    if(explLaunch(d)) {
-#define KC_L(K) hipLaunchKernelGGL(K, dim3(d.G), dim3(64), 0, st, dd, d.T)
-      KC_BY_ITEMS(KC_L, kAnalysisReport, true)
-      switch(laneItems(d.P)) {
-        case 2: KC_L(kAnalysisLoad<2>); break;
-        case 4: KC_L(kAnalysisLoad<4>); break;
-        default: KC_L(kAnalysisLoad<7>); break;
-      }
-#undef KC_L
-      KC_HIP(hipGetLastError());
-      return;
-    }
-    switch(laneItems(d.P)) {
-      case 2:
-        hipLaunchKernelGGL(kAnalysisReport<2>, dim3(d.G), dim3(64), 0, st, dd, d.T);
-        hipLaunchKernelGGL(kAnalysisLoad<2>, dim3(d.G), dim3(64), 0, st, dd, d.T);
-        break;
-      case 4:
-        hipLaunchKernelGGL(kAnalysisReport<4>, dim3(d.G), dim3(64), 0, st, dd, d.T);
-        hipLaunchKernelGGL(kAnalysisLoad<4>, dim3(d.G), dim3(64), 0, st, dd, d.T);
-        break;
-      default:
-        hipLaunchKernelGGL(kAnalysisReport<7>, dim3(d.G), dim3(64), 0, st, dd, d.T);
-        hipLaunchKernelGGL(kAnalysisLoad<7>, dim3(d.G), dim3(64), 0, st, dd, d.T);
-        break;
-    }
+    byItems(d.P, [&](auto ni) {
+      byFlag(explLaunch(d), [&](auto e) {
+        hipLaunchKernelGGL((kAnalysisReport<ni(), e()>), dim3(d.G), dim3(64), 0, st, dd, d.T);
+      });
+      hipLaunchKernelGGL(kAnalysisLoad<ni()>, dim3(d.G), dim3(64), 0, st, dd, d.T);
+    });
     KC_HIP(hipGetLastError());
     return;
   }
   const size_t lds = commitLdsBytes(d.cap);
-  const bool expl = explLaunch(d);
-#define KC_L(K) hipLaunchKernelGGL(K, dim3(d.G), dim3(64), lds, st, dd, d.T)
-  if(d.matchMode) {  // no kRows: match play writes no training rows
-    if(expl) {
-      KC_BY_ITEMS(KC_L, kCommit, true, true)
-    } else {
-      switch(laneItems(d.P)) {
-        case 2: hipLaunchKernelGGL((kCommit<2, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
-        case 4: hipLaunchKernelGGL((kCommit<4, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
-        default: hipLaunchKernelGGL((kCommit<7, true>), dim3(d.G), dim3(64), lds, st, dd, d.T); break;
-      }
-    }
+  byItems(d.P, [&](auto ni) {
+    byFlag(d.matchMode, [&](auto m) {
+      byFlag(explLaunch(d), [&](auto e) {
+        hipLaunchKernelGGL((kCommit<ni(), m(), e()>), dim3(d.G), dim3(64), lds, st, dd, d.T);
+      });
+    });
+  });
+  KC_HIP(hipGetLastError());
+  if(!d.matchMode) {  // match play writes no training rows
+    hipLaunchKernelGGL(kRows, dim3(d.G), dim3(64 * ROWS_WAVES), 0, st, dd, d.T);
     KC_HIP(hipGetLastError());
-    if(d.spN > 0) {
-      hipLaunchKernelGGL(kStartPosTurns, dim3(d.G), dim3(64), 0, st, dd, d.T);
-      KC_HIP(hipGetLastError());
-    }
-    return;
   }
-  if(expl) {
-    KC_BY_ITEMS(KC_L, kCommit, false, true)
-  } else {
-    switch(laneItems(d.P)) {
-      case 2: hipLaunchKernelGGL(kCommit<2>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;
-      case 4: hipLaunchKernelGGL(kCommit<4>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;
-      default: hipLaunchKernelGGL(kCommit<7>, dim3(d.G), dim3(64), lds, st, dd, d.T); break;
-    }
-  }
-#undef KC_L
-  KC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(kRows, dim3(d.G), dim3(64 * ROWS_WAVES), 0, st, dd, d.T);
-  KC_HIP(hipGetLastError());
   if(d.spN > 0) {  // a start-position table is set: the new games' turn records, after kRows
     hipLaunchKernelGGL(kStartPosTurns, dim3(d.G), dim3(64), 0, st, dd, d.T);
     KC_HIP(hipGetLastError());

@@ -34,7 +34,7 @@ __global__ void __launch_bounds__(512, 2) __attribute__((amdgpu_num_vgpr(KC_F8C_
   // fp16 activations in (0.25, 1); e4m3 plane bytes 0x30-0x3f (finite, ~0.5-1)
   for(int i = tid; i < G::PLANE_BYTES / 2; i += G::NT)
     act[i] = (uint16_t)(0x3400 + (i * 7 & 0x3ff));
-  for(int i = tid; i < G::PLANE2_BYTES; i += G::NT)
+  for(int i = tid; i < G::PLANE_BYTES; i += G::NT)  // the second plane, the hi plane's size
     reinterpret_cast<uint8_t*>(smem)[G::PLANE_BYTES + i] = (uint8_t)(0x30 + (i & 15));
   constexpr int CH = G::tapPieces(3);
   stageChunk<G::NW>(w, ldsAddr(wl) + G::WSLOT * 16, CH, wave, lane);  // conv 1's chunk 0: slot 1
