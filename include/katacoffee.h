@@ -727,6 +727,70 @@ int coffee_selfplay_set_root_search(coffee_selfplay* h, const coffee_root_search
 int coffee_analysis_set_root_search(coffee_analysis* h, const coffee_root_search_params* p);
 int coffee_match_set_root_search(coffee_match* h, int side, const coffee_root_search_params* p);
 
+/* ---- parallel playouts per search (the reference's numSearchThreads, 16 per
+ *      analysis thread in its analysis set-up, and numVirtualLossesPerThread) ----
+ * An analysis engine's setting: latency of one query against throughput of many.  With
+ * threads = K a searching slot makes n = min(K, visit limit - root visits) descents a round, one
+ * after the other in the order j = 0 .. n-1, and all their leaves go through the network in the
+ * round's one batch (descent j of slot g on row g K + j); the backups then run in the same order,
+ * and the visit limit is tested once after the last.  A search never overshoots its limit.
+ * Virtual losses: every node a descent enters as a child -- its leaf included -- counts one more
+ * until that playout's backup.  A child with vl > 0 of them is valued, after the choice between
+ * its utility and the first-play urgency and before futile-visit pruning, the
+ * rootDesiredPerChildVisits funnel and wide root noise, as
+ *   vlw = vl * per_thread;  frac = vlw / (vlw + max(0.25, w));
+ *   u = u + (loss - u) * frac;  w = w + vlw        loss: -1 white to move at the parent, +1 black
+ * The parent's total child weight, the largest child weight and the new-child candidate do not
+ * see them.  Collision: a descent that selects a child still in flight -- a node an earlier
+ * descent of the round allocated, not yet evaluated; also through a transposition, which then
+ * adds no edge -- is abandoned: its virtual losses come off at once, it counts no visit and
+ * takes no row, and the slot makes no further descent that round.  Draws keyed on the root's
+ * visits (wide root noise) are the same for the descents of one round.  Every other phase of a
+ * slot stays one evaluation a round.  Results are deterministic and independent of the slot
+ * count.  threads = 1 (the default) is the engine without the feature, bit for bit. */
+#define COFFEE_SEARCH_THREADS_MAX 32
+#define COFFEE_ROUND_PATH_MAX 102 /* levels of a path: board area + 2 */
+/* leaf_kind of coffee_round_path */
+#define COFFEE_LEAF_NN 1        /* a new node, evaluated by the network this round */
+#define COFFEE_LEAF_TERMINAL 2  /* a finished game */
+#define COFFEE_LEAF_CATCHUP 3   /* an edge with fewer visits than its node (graph search) */
+#define COFFEE_LEAF_NOCHILD 4   /* no selectable child: the node's own evaluation again */
+#define COFFEE_LEAF_CACHED 6    /* a new node, evaluation taken from the NN cache */
+#define COFFEE_LEAF_COLLISION 12
+typedef struct coffee_search_threads_info {
+  int32_t threads;
+  float virtual_losses_per_thread;
+  uint64_t descents;            /* descents started so far, abandoned ones included */
+  uint64_t collisions;          /* descents abandoned at a collision so far */
+  uint64_t live_virtual_losses; /* virtual losses now in the engine's trees (0 between rounds) */
+} coffee_search_threads_info;
+/* One descent: path_len levels (node, child slot taken there) from the root down; node is the
+ * slot's internal node index (equal where two entries name one node; level 0 is the root).  A
+ * collision carries one more entry, at [path_len]: the node and the child slot it collided at. */
+typedef struct coffee_round_path {
+  int32_t leaf_kind, path_len;
+  int32_t node[COFFEE_ROUND_PATH_MAX];
+  int32_t child_slot[COFFEE_ROUND_PATH_MAX];
+} coffee_round_path;
+typedef struct coffee_round_paths {
+  int32_t num_descents; /* of the slot's last round; 0 when that round was no search round */
+  int32_t pad;
+  coffee_round_path path[COFFEE_SEARCH_THREADS_MAX];
+} coffee_round_paths;
+/* threads in 1..COFFEE_SEARCH_THREADS_MAX, virtual_losses_per_thread finite and > 0.  Allowed
+ * only while the engine holds no query (every submitted query has its result), COFFEE_EINVAL
+ * otherwise.  A round must fit one network launch: COFFEE_EINVAL when num_slots * threads
+ * exceeds the batch cap (nn_batch_cap, else the network's own), coffee_last_error() naming both.
+ * A refused call leaves the engine as it was.  The arrays are allocated on first use. */
+int coffee_analysis_set_search_threads(coffee_analysis* h, int threads, float virtual_losses_per_thread);
+int coffee_analysis_search_threads_info(coffee_analysis* h, coffee_search_threads_info* out);
+/* The descents of a slot's last round (host output; synchronises the engine stream). */
+int coffee_analysis_round_paths(coffee_analysis* h, int slot, coffee_round_paths* out);
+/* The valuation above on the host (no device is touched), bit for bit what the kernels compute:
+ * mover 1 black / 2 white to move at the parent.  vl = 0 returns utility and weight unchanged. */
+int coffee_virtual_loss(float per_thread, uint32_t vl, int mover, float utility, float weight, float* u_out,
+                        float* w_out);
+
 /* ---- per-side match settings (the reference's `katago match`, whose search keys
  *      take a bot suffix, cpp/command/match.cpp) ----
  * A match engine whose two sides search with their own parameters and uncertainty weighting,

@@ -141,6 +141,28 @@ class RootSearchParams(ctypes.Structure):
     _fields_ = [("wide_root_noise", ctypes.c_float), ("futile_visits_threshold", ctypes.c_float)]
 
 
+SEARCH_THREADS_MAX = 32
+ROUND_PATH_MAX = 102
+LEAF_NN, LEAF_TERMINAL, LEAF_CATCHUP, LEAF_NOCHILD, LEAF_CACHED, LEAF_COLLISION = 1, 2, 3, 4, 6, 12
+
+
+class SearchThreadsInfo(ctypes.Structure):
+    """coffee_search_threads_info: parallel playouts per search."""
+    _fields_ = [("threads", ctypes.c_int32), ("virtual_losses_per_thread", ctypes.c_float),
+                ("descents", ctypes.c_uint64), ("collisions", ctypes.c_uint64),
+                ("live_virtual_losses", ctypes.c_uint64)]
+
+
+class RoundPath(ctypes.Structure):
+    _fields_ = [("leaf_kind", ctypes.c_int32), ("path_len", ctypes.c_int32),
+                ("node", ctypes.c_int32 * ROUND_PATH_MAX), ("child_slot", ctypes.c_int32 * ROUND_PATH_MAX)]
+
+
+class RoundPaths(ctypes.Structure):
+    """coffee_round_paths: the descents of a slot's last round."""
+    _fields_ = [("num_descents", ctypes.c_int32), ("pad", ctypes.c_int32), ("path", RoundPath * SEARCH_THREADS_MAX)]
+
+
 class MatchSide(ctypes.Structure):
     """coffee_match_side: one side's search parameters and uncertainty weighting."""
     _fields_ = [("search", SearchParams), ("unc", UncertaintyParams)]
@@ -250,6 +272,8 @@ EXPORTS = [
     "coffee_selfplay_game_tree_priors", "coffee_match_game_tree_priors", "coffee_analysis_game_tree_priors",
     "coffee_root_search_params_default", "coffee_wide_root_noise", "coffee_futile_visits",
     "coffee_selfplay_set_root_search", "coffee_analysis_set_root_search", "coffee_match_set_root_search",
+    "coffee_analysis_set_search_threads", "coffee_analysis_search_threads_info", "coffee_analysis_round_paths",
+    "coffee_virtual_loss",
 ]
 
 
@@ -391,6 +415,12 @@ def lib():
             L.coffee_selfplay_set_root_search.argtypes = [c_p, c_p]
             L.coffee_analysis_set_root_search.argtypes = [c_p, c_p]
             L.coffee_match_set_root_search.argtypes = [c_p, c_i, c_p]
+        if hasattr(L, "coffee_virtual_loss"):  # (absent in earlier builds run as A/B references)
+            L.coffee_analysis_set_search_threads.argtypes = [c_p, c_i, ctypes.c_float]
+            L.coffee_analysis_search_threads_info.argtypes = [c_p, c_p]
+            L.coffee_analysis_round_paths.argtypes = [c_p, c_i, c_p]
+            L.coffee_virtual_loss.argtypes = [ctypes.c_float, ctypes.c_uint32, c_i, ctypes.c_float, ctypes.c_float,
+                                              c_p, c_p]
         _lib = L
     return _lib
 
@@ -403,6 +433,17 @@ def check(rc):
 
 def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
+
+
+def virtual_loss(per_thread, vl, mover, utility, weight):
+    """(utility, weight) of a child that vl unfinished playouts of the round have entered, as its
+    parent's selection values it (coffee_virtual_loss, the host run of the kernels' code): mover 1
+    black / 2 white to move at the parent.  f32 results; vl = 0 returns the inputs."""
+    u, w = ctypes.c_float(), ctypes.c_float()
+    check(lib().coffee_virtual_loss(ctypes.c_float(float(per_thread)), int(vl), int(mover),
+                                    ctypes.c_float(float(utility)), ctypes.c_float(float(weight)),
+                                    ctypes.byref(u), ctypes.byref(w)))
+    return np.float32(u.value), np.float32(w.value)
 
 
 def default_search_params(**over):
@@ -1379,7 +1420,7 @@ class Analysis:
     def __init__(self, X=5, Y=5, W=4, num_slots=64, model_path=None, search=None, seed=1, node_cap=0,
                  commit_interval=0, nn_cache_log2=0, nn_batch_cap=0, nn_precision="default", engines_per_device=0,
                  query_capacity=0, max_pv_len=ANALYSIS_MAX_PV, root_symmetry_pruning=False, include_policy=False,
-                 **search_over):
+                 search_threads=1, virtual_losses_per_thread=1.0, **search_over):
         self.X, self.Y, self.W = X, Y, W
         self.root_symmetry_pruning, self.include_policy = False, False
         self.A, self.P = X * Y, 4 * X * Y
@@ -1408,6 +1449,44 @@ class Analysis:
         check(lib().coffee_analysis_create(ctypes.byref(cfg), ctypes.byref(self.h)))
         if root_symmetry_pruning or include_policy:
             self.set_root_options(root_symmetry_pruning, include_policy)
+        self.search_threads = 1
+        if search_threads != 1 or virtual_losses_per_thread != 1.0:
+            try:
+                self.set_search_threads(search_threads, virtual_losses_per_thread)
+            except CoffeeError:
+                self.close()
+                raise
+
+    def set_search_threads(self, threads, virtual_losses_per_thread=1.0):
+        """Parallel playouts per search (coffee_analysis_set_search_threads): up to `threads`
+        descents of a searching slot a round, steered apart by virtual losses.  Only while the
+        engine holds no query; num_slots x threads must fit one network launch."""
+        check(lib().coffee_analysis_set_search_threads(self.h, int(threads),
+                                                       ctypes.c_float(float(virtual_losses_per_thread))))
+        self.search_threads = int(threads)
+
+    def search_threads_info(self):
+        """coffee_analysis_search_threads_info as a dict: threads, virtual_losses_per_thread,
+        descents, collisions, live_virtual_losses."""
+        s = SearchThreadsInfo()
+        check(lib().coffee_analysis_search_threads_info(self.h, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in SearchThreadsInfo._fields_}
+
+    def round_paths(self, slot):
+        """The descents of the slot's last round (coffee_analysis_round_paths), in order: dicts of
+        leaf_kind (LEAF_*), nodes and child_slots (one entry per path level from the root down)
+        and, for a LEAF_COLLISION, collision = (node, child slot) it was abandoned at."""
+        r = RoundPaths()
+        check(lib().coffee_analysis_round_paths(self.h, int(slot), ctypes.byref(r)))
+        out = []
+        for j in range(r.num_descents):
+            p = r.path[j]
+            d = {"leaf_kind": p.leaf_kind, "nodes": list(p.node[:p.path_len]),
+                 "child_slots": list(p.child_slot[:p.path_len]), "collision": None}
+            if p.leaf_kind == LEAF_COLLISION:
+                d["collision"] = (p.node[p.path_len], p.child_slot[p.path_len])
+            out.append(d)
+        return out
 
     def submit(self, queries, restricts=None):
         """Queues queries; returns how many were accepted (the first ones): submitted minus

@@ -1056,6 +1056,43 @@ int coffee_match_set_root_search(coffee_match* h, int side, const coffee_root_se
   });
 }
 
+// ---- parallel playouts per search (vloss.h: the sequence the kernels run) ----
+
+int coffee_analysis_set_search_threads(coffee_analysis* h, int threads, float virtual_losses_per_thread) {
+  return guarded([&] {
+    need(h && h->eng, "NULL handle");
+    h->eng->setSearchThreads(threads, virtual_losses_per_thread);
+  });
+}
+
+int coffee_analysis_search_threads_info(coffee_analysis* h, coffee_search_threads_info* out) {
+  return guarded([&] {
+    need(h && h->eng && out, "NULL argument");
+    h->eng->searchThreadsInfo(*out);
+  });
+}
+
+int coffee_analysis_round_paths(coffee_analysis* h, int slot, coffee_round_paths* out) {
+  return guarded([&] {
+    need(h && h->eng && out, "NULL argument");
+    h->eng->roundPaths(slot, *out);
+  });
+}
+
+int coffee_virtual_loss(float per_thread, uint32_t vl, int mover, float utility, float weight, float* u_out,
+                        float* w_out) {
+  return guarded([&] {
+    need(mover == 1 || mover == 2, "mover must be 1 (black) or 2 (white)");
+    need(per_thread > 0.0f && std::isfinite(per_thread), "per_thread must be finite and > 0");
+    float u = utility, w = weight;
+    virtualLossAdjust(per_thread, vl, mover, u, w);
+    if(u_out)
+      *u_out = u;
+    if(w_out)
+      *w_out = w;
+  });
+}
+
 // ---- start positions (startpos.h: the thresholds and the pick the kernels run) ----
 
 void coffee_start_positions_params_default(coffee_start_positions_params* p) {

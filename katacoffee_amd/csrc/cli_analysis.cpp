@@ -298,6 +298,7 @@ int analysisMain(int argc, char** argv) {
   int slots = 64, pvLen = 15;  // analysis_example.cfg: analysisPVLen 15
   try {
     applyConfig(kv, s);
+    applySearchThreadsConfig(ConfigReader{kv, ""}, s.searchThreads, s.virtualLossesPerThread);
     for(auto kd : {std::make_pair("numAnalysisSlots", &slots), std::make_pair("analysisPVLen", &pvLen)}) {
       auto it = kv.find(kd.first);
       if(it == kv.end())
@@ -331,6 +332,9 @@ int analysisMain(int argc, char** argv) {
   must(coffee_analysis_set_uncertainty(sv.h, &s.unc), "set uncertainty");
   must(coffee_analysis_set_exploration(sv.h, &s.ex), "set exploration");
   must(coffee_analysis_set_root_search(sv.h, &s.rs), "set root search");
+  // a round of numAnalysisSlots x threads rows must fit one network launch
+  if(coffee_analysis_set_search_threads(sv.h, s.searchThreads, s.virtualLossesPerThread) != COFFEE_OK)
+    fail(std::string("config key numSearchThreadsPerAnalysisThread: ") + coffee_last_error());
   // the policy travels with every result: a query's includePolicy prints it, and the symmetry
   // copies read the legal moves off it
   const coffee_analysis_root_options ro{s.rootSymmetryPruning, 1};
@@ -343,6 +347,9 @@ int analysisMain(int argc, char** argv) {
   sv.maxVisitsCap = s.sp.max_visits;  // the node pools are sized for the config's visits
   fprintf(stderr, "katago analysis: %dx%d win %d, %d slots, %d visits, %s\n", s.x, s.y, s.winLen, slots,
           s.sp.max_visits, model.empty() ? "stand-in network" : model.c_str());
+  if(s.searchThreads > 1)
+    fprintf(stderr, "katago analysis: %d search threads per slot, %g virtual losses per thread\n", s.searchThreads,
+            (double)s.virtualLossesPerThread);
   std::vector<coffee_analysis_result> hdr((size_t)c.query_capacity);
   std::vector<coffee_analysis_move> mv((size_t)c.query_capacity * sv.P);
   std::vector<coffee_analysis_root_info> rinfo((size_t)c.query_capacity);

@@ -73,6 +73,11 @@ struct Settings {
   // rootSymmetryPruning (`katago analysis` only): off unless the config turns it on -- the
   // reference's loader defaults it on for analysis and GTP (setup.cpp:639-644)
   int32_t rootSymmetryPruning = 0;
+  // numSearchThreadsPerAnalysisThread (alias numSearchThreads) and numVirtualLossesPerThread
+  // (DESIGN.md 8j), read by `katago analysis` alone (applySearchThreadsConfig): one playout a
+  // round unless the config asks for more (the reference's analysis example sets 16)
+  int searchThreads = 1;
+  float virtualLossesPerThread = 1.0f;
   StartPosSettings startPos;  // off unless startPosesProb > 0 and a source is named
 };
 
@@ -257,6 +262,20 @@ inline void applyExplorationConfig(const ConfigReader& r, coffee_exploration_par
 inline void applyRootSearchConfig(const ConfigReader& r, coffee_root_search_params& rs) {
   r.getfIn("wideRootNoise", rs.wide_root_noise, 0.0f, 5.0f);
   r.getfIn("futileVisitsThreshold", rs.futile_visits_threshold, 0.01f, 1.0f);
+}
+
+// The parallel-playout keys: numSearchThreadsPerAnalysisThread in 1..32, under its
+// short name numSearchThreads where the file has only that, and numVirtualLossesPerThread with
+// the reference's range (setup.cpp: 0.01 to 1000).  `katago analysis` alone calls this, after
+// applyConfig: the other commands make one playout a round and go on ignoring the keys, which the
+// reference's self-play, match and gatekeeper configs carry with values of their own.
+inline void applySearchThreadsConfig(const ConfigReader& r, int& threads, float& perThread) {
+  const char* key = r.has("numSearchThreadsPerAnalysisThread") ? "numSearchThreadsPerAnalysisThread" : "numSearchThreads";
+  r.geti(key, threads);
+  if(threads < 1 || threads > COFFEE_SEARCH_THREADS_MAX)
+    throw std::invalid_argument(std::string("config key ") + key + ": value " + std::to_string(threads) +
+                                " outside [1, " + std::to_string(COFFEE_SEARCH_THREADS_MAX) + "]");
+  r.getfIn("numVirtualLossesPerThread", perThread, 0.01f, 1000.0f);
 }
 
 inline void applyConfig(const std::map<std::string, std::string>& kv, Settings& s) {

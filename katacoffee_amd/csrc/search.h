@@ -28,6 +28,7 @@
 #include "uncertainty.h"
 #include "explore.h"
 #include "rootsearch.h"
+#include "vloss.h"
 
 namespace kc {
 
@@ -71,7 +72,11 @@ enum LeafKind {
   LEAF_SIDE = 9,    // side-position continuation: the position after the search's response
   // fused backup + select (kBackupSelect): the leaf's cache slot is being written by this
   // round's backups, so the lookup waits for kResolve (which runs after them)
-  LEAF_PENDING = 10
+  LEAF_PENDING = 10,
+  // parallel playouts: the slot's state between a wide selection and its backup
+  // (the leaves are in SearchDev::wideRec), and a descent abandoned at a node still in flight
+  LEAF_WIDE = 11,
+  LEAF_COLLISION = 12
 };
 
 // NN evaluation cache slot of a state key (SPEC a7; oracle ora_search.cpp cacheSlot).
@@ -146,8 +151,10 @@ struct Node {
   // with the node record: prior and policy position (0xFFFF: every legal move expanded)
   float nextPrior;
   uint16_t nextPos;
-  uint16_t pad0;
-  uint32_t edgeBase;              // the node's block of child slots >= INLINE_EDGES in the edge pool
+  // unfinished playouts of the current round that have entered this node (parallel playouts,
+  // DESIGN.md 8j; 0 outside a wide round)
+  uint16_t virtualLosses;
+  uint32_t edgeBase;             // the node's block of child slots >= INLINE_EDGES in the edge pool
   // the weight of the node's own evaluation in its averages (uncertainty weighting, DESIGN.md
   // 8c; 1 with the setting off), written with nnWin / nnLoss
   float nnWeight;
@@ -260,6 +267,18 @@ struct GameDev {
   int32_t spPending;
   float accWin, accLoss, rawWin, rawLoss;
 };
+
+// Parallel playouts: the leaf of descent j of a slot's wide round, kept from the
+// selection to the backup -- the GameDev fields a single playout's leaf lives in.
+struct WideRec {
+  DBoard leaf;
+  int32_t leafKind, leafNode, leafSym, nnSlot;
+  int32_t cSlot, pathLen;
+  float cHitWin, cHitLoss, cHitErr;
+  int32_t pad;
+};
+// SearchDev::wideCtr entries: descents made, descents abandoned at a collision.
+enum WideCounter { WC_DESCENTS = 0, WC_COLLISIONS, WC_N };
 
 // Device array pointer of SearchDev: on the device every access goes through a
 // global-address-space pointer, so the compiler emits global_load/store (ordered,
@@ -421,6 +440,17 @@ struct SearchDev {
   // 8h), read by the EXPL kernel instantiations only, at the root's selection: rs beside ex, rs1
   // beside ex1.
   RootSearch rs, rs1;
+  // parallel playouts per search (coffee_analysis_set_search_threads; vloss.h), read
+  // by the wide kernels only (kSelectWide, kCompactWide, kBackupWide).  wideK <= 1: off, the
+  // launchers pick the kernels above and none of these is allocated.  With wideK = K descent j of
+  // slot g owns network row g K + j: nnIn, nnOut, nnNeed, nnBid and nnIdx then hold G K rows.
+  int32_t wideK;
+  float vlPerThread;                  // numVirtualLossesPerThread
+  DPtr<WideRec> wideRec;              // [G][K] the leaves of the slot's current round
+  DPtr<int32_t> widePathNode;         // [G][K][MAX_DEPTH] their paths
+  DPtr<int32_t> widePathSlot;
+  DPtr<int32_t> wideCount;            // [G] descents of the slot's last wide round, an abandoned one included
+  DPtr<unsigned long long> wideCtr;   // [WC_N] running counts (WideCounter)
 };
 
 // Match play: the candidate (net 1) plays black (player 1) in game number n of global
@@ -460,6 +490,9 @@ void launchResolve(const SearchDev& d, const SearchDev* dd, hipStream_t st);
 void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st);  // + kRows
 // (d.analysisMode: launchSelfplayInit leaves every slot idle, and launchCommit passes d.aSubmitted
 // to the device, reports the listed searches and lets the idle slots pop queued queries)
+// The live virtual losses of every slot's tree, summed into *out (device, zeroed first).
+void launchVirtualLossCount(const SearchDev& d, const SearchDev* dd, unsigned long long* out, hipStream_t st)
+    __attribute__((weak));
 void launchGameTree(const SearchDev* dd, int slot, int maxNodes, uint32_t* nodesOut, uint32_t* edgesOut,
                     int32_t* count, hipStream_t st);
 // The priors beside launchGameTree's export, same node order: priorsOut [maxNodes][P] f32 bits

@@ -148,9 +148,20 @@ struct GV {
   const SP* sp;  // this move's search parameters (moveParams after loadGame)
   const Unc* unc;  // and its uncertainty weighting (match play: the searching side's, bindGame)
   mutable int esel = 0;  // the game's current edge-pool buffer (GameDev::edgeSel; setEdgeSel)
-  KC_D GV(const SearchDev& d_, int g_) : d(d_), T(*d_.T), g(g_), lane(laneId()), sp(&d_.sp), unc(&d_.unc) {}
+  // the playout's network row and path arrays: the game's own, or descent j's of a wide round
+  // (setDescent)
+  int row;
+  int32_t* wpn = nullptr;
+  int32_t* wps = nullptr;
+  KC_D GV(const SearchDev& d_, int g_) : d(d_), T(*d_.T), g(g_), lane(laneId()), sp(&d_.sp), unc(&d_.unc), row(g_) {}
   // tables through a readonly noalias kernel argument: uniform reads become scalar loads
-  KC_D GV(const SearchDev& d_, const DTables& t_, int g_) : d(d_), T(t_), g(g_), lane(laneId()), sp(&d_.sp), unc(&d_.unc) {}
+  KC_D GV(const SearchDev& d_, const DTables& t_, int g_)
+      : d(d_), T(t_), g(g_), lane(laneId()), sp(&d_.sp), unc(&d_.unc), row(g_) {}
+  KC_D void setDescent(int j) {
+    row = g * d.wideK + j;
+    wpn = d.widePathNode + (size_t)row * MAX_DEPTH;
+    wps = d.widePathSlot + (size_t)row * MAX_DEPTH;
+  }
   KC_D Node* nodes() const { return d.nodes + (size_t)g * d.cap; }
   KC_D Edge* inlineEdges(int n) const { return d.edges + ((size_t)g * d.cap + n) * INLINE_EDGES; }
   KC_D Edge* edgePool() const { return d.edgePool + ((size_t)g * 2 + esel) * d.edgePoolCap; }
@@ -168,8 +179,8 @@ struct GV {
   KC_D float* accPolicy() const { return d.accPolicy + (size_t)g * d.P; }
   KC_D float* rawPolicy() const { return d.rawPolicy + (size_t)g * d.P; }
   KC_D float* rootNoised() const { return d.rootNoised + (size_t)g * d.P; }
-  KC_D int32_t* pathNode() const { return d.pathNode + (size_t)g * MAX_DEPTH; }
-  KC_D int32_t* pathSlot() const { return d.pathSlot + (size_t)g * MAX_DEPTH; }
+  KC_D int32_t* pathNode() const { return wpn ? wpn : d.pathNode + (size_t)g * MAX_DEPTH; }
+  KC_D int32_t* pathSlot() const { return wps ? wps : d.pathSlot + (size_t)g * MAX_DEPTH; }
   KC_D TurnRec* turns() const { return d.turns + (size_t)g * d.maxTurns; }
   KC_D int16_t* turnPol(int t) const { return d.turnPol + ((size_t)g * d.maxTurns + t) * d.P; }
 };
@@ -366,7 +377,7 @@ KC_D int allocNode(const GV& v, GameDev& s, int nextPla, uint64_t k0, uint64_t k
     n.flags = terminal ? 2 : 0;
     n.nextPrior = -1.0f;
     n.nextPos = 0xFFFF;
-    n.pad0 = 0;
+    n.virtualLosses = 0;
     n.edgeBase = 0;
     n.nnWeight = 1.0f;
     v.nodes()[idx] = n;
@@ -871,7 +882,9 @@ KC_D float exploreScaling(const SP& sp, float totalChildWeight) {
 // oracle selectBest (selectBestChildToDescend searchexplorehelpers.cpp:304-451)
 // Also returns the chosen existing child's edge and the child's visits and flags,
 // broadcast from the lane that holds them (no reload of either after the choice).
-template <int NI, bool EXPL = false>
+// (VL, the wide kernels' flag -- DESIGN.md 8j: a child's virtual losses enter its value and weight,
+// vloss.h; every other instantiation holds no trace of them)
+template <int NI, bool EXPL = false, bool VL = false>
 KC_D int selectBest(const GV& v, const GameDev& s, int ni, const Node& n, const float* pol, bool isRoot, int& newPos,
                     uint32_t* hasBits, const Edge& e0, Edge& ce, uint32_t& cVisits, uint32_t& cFlags) {
   const SP& sp = *v.sp;
@@ -889,12 +902,15 @@ KC_D int selectBest(const GV& v, const GameDev& s, int ni, const Node& n, const 
   const Node* NS = v.nodes();
   float probs[NI], cw[NI], pv[NI], cu[NI];
   uint32_t cvis[NI], cfl[NI];
+  [[maybe_unused]] uint32_t cvl[NI];
   Edge ev[NI];
 #pragma unroll
   for(int j = 0; j < NI; j++) {
     int i = v.lane + 64 * j;
     probs[j] = cw[j] = pv[j] = cu[j] = 0.0f;
     cvis[j] = cfl[j] = 0;
+    if constexpr(VL)
+      cvl[j] = 0;
     ev[j] = Edge{0u, 0u, 0.0f, 0u};
     if(j > 0 && 64 * j >= k)  // uniform: no lane has an item here
       continue;
@@ -905,6 +921,8 @@ KC_D int selectBest(const GV& v, const GameDev& s, int ni, const Node& n, const 
       float p = isRoot ? pol[e.move] : e.prior;
       cvis[j] = c.visits;
       cfl[j] = c.flags;
+      if constexpr(VL)
+        cvl[j] = c.virtualLosses;
       cu[j] = c.utilityAvg;
       pv[j] = p;
       probs[j] = p < 0.0f ? 0.0f : p;
@@ -960,6 +978,8 @@ KC_D int selectBest(const GV& v, const GameDev& s, int ni, const Node& n, const 
     else {
       float w = cw[j];
       float u = (cvis[j] == 0 || w <= 0.0f) ? fpu : cu[j];
+      if constexpr(VL)
+        virtualLossAdjust(v.d.vlPerThread, cvl[j], pla, u, w);
       bool futile = false;
       if constexpr(EXPL)
         futile = rsThr > 0.0f && futileChild(rsThr, rsMaxW, rsWpv, rsLeft, ev[j].visits, cvis[j], w);
@@ -1081,10 +1101,52 @@ KC_D void nextExpansion(const GV& v, const float (&pv)[NI], float curPrior, int 
   nPos = bi != BIG ? bi : 0xFFFF;
 }
 
+// Parallel playouts: a node entered as a child carries one more virtual loss until
+// the playout's backup (or its collision) takes it off again.  Lane 0 alone writes the count.
+// (The barrier keeps lane 0's branch apart from the all-lane updates of the game's LDS copy
+// before it: merged into one divergent region, lane 0 would run those a second time.)
+KC_D void addVirtualLoss(const GV& v, int node) {
+  waveSync();
+  if(v.lane == 0)
+    v.nodes()[node].virtualLosses += 1;
+}
+// The virtual losses of a playout whose path holds pathLen levels and ends at node `last` come
+// off: it entered the path's nodes below the root and `last` (nothing when it never left the
+// root).  The nodes of a path are distinct, so each lane takes one.
+KC_D void removeVirtualLosses(const GV& v, int pathLen, int last) {
+  waveSync();
+  const int32_t* pn = v.pathNode();
+  for(int i = v.lane; i < pathLen; i += 64)
+    v.nodes()[i + 1 < pathLen ? pn[i + 1] : last].virtualLosses -= 1;
+  waveSync();
+}
+
+// One more level on the playout's path.  The game's LDS copy is updated by all lanes at once,
+// each writing the same value.  The VL instantiations follow the update with a lane-0 branch
+// (addVirtualLoss): there every lane takes the new length into a register first and writes it
+// between barriers, so a lane that ran the update apart from the others would still write the
+// same value -- the result does not depend on where the compiler places the code.
+template <bool VL>
+KC_D void pushLevel(GameDev& s) {
+  if constexpr(VL) {
+    const int len = s.pathLen + 1;
+    waveSync();
+    s.pathLen = len;
+    waveSync();
+  } else {
+    s.pathLen++;
+  }
+}
+
 // oracle descend (playoutDescend search.cpp:936-1165, allocateOrFindNode :704-759,
 // maybeCatchUpEdgeVisits :1169-1207)
-template <int NI, bool EXPL = false>
-KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* LDS [P] */) {
+// VL (the wide kernels): one of a round's several descents.  The selections see the
+// virtual losses of the descents before it, every node it enters gains one, and a child still
+// in flight -- allocated by an earlier descent of the round, not evaluated yet -- ends it as
+// LEAF_COLLISION at the parent, nothing linked or entered there.  loadRootPol: the root's noised
+// policy is not in rootPol yet (the round's first descent).
+template <int NI, bool EXPL = false, bool VL = false>
+KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* LDS [P] */, bool loadRootPol = true) {
   constexpr bool W1 = W1_OF<NI>;
   const SP& sp = *v.sp;
   const DTables& T = v.T;
@@ -1103,7 +1165,7 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
   Node n = v.nodes()[ni];
   // the node an expansion will take (one expansion ends a descent)
   const int freeIdx = s.freeTop > 0 ? (int)v.freeList()[s.freeTop - 1] : -1;
-  {
+  if(!VL || loadRootPol) {
     // the root's noised policy into LDS: the root selection gathers it per child and
     // scans it for the best unexpanded move
     const float* rn = v.rootNoised();
@@ -1145,8 +1207,9 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
     // a node with at most 64 children (every non-root level in practice, the root until
     // its 65th child) takes the one-item form: an empty second item adds nothing to the
     // sums and never wins the (value, index) argmax, so the results are the same
-    int slot = n.numChildren <= 64 ? selectBest<1, EXPL>(v, s, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags)
-                                   : selectBest<NI, EXPL>(v, s, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags);
+    int slot = n.numChildren <= 64
+                   ? selectBest<1, EXPL, VL>(v, s, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags)
+                   : selectBest<NI, EXPL, VL>(v, s, ni, n, pol, isRoot, newPos, hasBits, e0, ce, cVisits, cFlags);
     SPROF_ADD(5, SPROF_NOW() - tSel);
     (void)tSel;
     if(slot < 0) {
@@ -1212,6 +1275,19 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
       int ttSlot = -1;
       int child = sp.useGraph ? ttFind(v, k0, k1, ttSlot) : -1;
       const bool fresh = child < 0;
+      if constexpr(VL) {
+        // a transposition onto a node in flight: the playout fails before the edge exists
+        if(!fresh && (v.nodes()[child].flags & 3) == 0) {
+          s.edgeTop -= reserved;
+          if(v.lane == 0) {  // where it collided, past the path's end (coffee_analysis_round_paths)
+            v.pathNode()[s.pathLen] = ni;
+            v.pathSlot()[s.pathLen] = slot;
+          }
+          s.leafKind = LEAF_COLLISION;
+          s.leafNode = ni;
+          break;
+        }
+      }
       float nxtPrior = -1.0f;
       int nxtPos = 0xFFFF;
       if(!isRoot)
@@ -1245,8 +1321,10 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
         v.pathNode()[s.pathLen] = ni;
         v.pathSlot()[s.pathLen] = slot;
       }
-      s.pathLen++;
+      pushLevel<VL>(s);
       waveSync();
+      if constexpr(VL)
+        addVirtualLoss(v, child);
       SPROF_ADD(6, SPROF_NOW() - tExp);
       // a fresh node has no visits and the terminal flag of b; a transposition's
       // record is read
@@ -1263,11 +1341,24 @@ KC_D void descend(const GV& v, GameDev& s, uint32_t* hasBits, float* rootPol /* 
       break;
     }
     const int child = (int)ce.child;
+    if constexpr(VL) {
+      if((cFlags & 3) == 0) {  // in flight (no node without visits is expanded)
+        if(v.lane == 0) {
+          v.pathNode()[s.pathLen] = ni;
+          v.pathSlot()[s.pathLen] = slot;
+        }
+        s.leafKind = LEAF_COLLISION;
+        s.leafNode = ni;
+        break;
+      }
+    }
     if(v.lane == 0) {
       v.pathNode()[s.pathLen] = ni;
       v.pathSlot()[s.pathLen] = slot;
     }
-    s.pathLen++;
+    pushLevel<VL>(s);
+    if constexpr(VL)
+      addVirtualLoss(v, child);
     if(ce.visits < cVisits) {
       s.leafKind = LEAF_CATCHUP;
       s.leafNode = child;
@@ -1363,12 +1454,11 @@ KC_D void cacheLookup(const GV& v, GameDev& s, bool fused) {
   }
 }
 
-// The end of a selection: an NN leaf draws its symmetry, the game's batch row is encoded
-// when the leaf needs the network, and the game state is stored.
+// The end of a descent or of another phase's evaluation request: an NN leaf draws its symmetry
+// and the playout's batch row (GV::row) is encoded when the leaf needs the network.
 template <bool W1>
-KC_D void finishSelect(const GV& v, GameDev& s, DRng& rng) {
+KC_D void finishLeaf(const GV& v, GameDev& s, DRng& rng) {
   const SearchDev& d = v.d;
-  const int g = v.g;
   if(s.leafKind == LEAF_NN)
     s.leafSym = (int)rng.below(8);
   s.rngCtr = rng.ctr;
@@ -1376,18 +1466,24 @@ KC_D void finishSelect(const GV& v, GameDev& s, DRng& rng) {
       s.leafKind == LEAF_NN || s.leafKind == LEAF_ROOTEVAL || s.leafKind == LEAF_INIT || s.leafKind == LEAF_FORK ||
       s.leafKind == LEAF_SIDE;
   if(v.lane == 0) {
-    d.nnNeed[g] = needNN ? 1 : 0;
+    d.nnNeed[v.row] = needNN ? 1 : 0;
     if(needNN)
-      d.nnBid[g] = s.leafKind == LEAF_NN && d.cacheOn ? (uint32_t)s.cSlot : ~0u;
+      d.nnBid[v.row] = s.leafKind == LEAF_NN && d.cacheOn ? (uint32_t)s.cSlot : ~0u;
   }
   if(needNN) {
     // the game's own batch row: no shared counter (a same-address atomic from
     // every block serialises at L2); kCompact lists the rows the network evaluates
-    const int slot = g;
+    const int slot = v.row;
     s.nnSlot = slot;
     s.nnEvals++;
     encodePackedWave<W1>(v.T, s.leaf, s.leafSym, d.nnIn + (size_t)slot * d.inWords);
   }
+}
+
+// The end of a selection: finishLeaf, and the game state is stored.
+template <bool W1>
+KC_D void finishSelect(const GV& v, GameDev& s, DRng& rng) {
+  finishLeaf<W1>(v, s, rng);
   waveSync();
   storeGame(v, s);
 }
@@ -1396,15 +1492,17 @@ KC_D void finishSelect(const GV& v, GameDev& s, DRng& rng) {
 // (the fused kernel's backup just ran; every path below then stores it).  rootPol: LDS [MAX_P].
 template <int NI, bool MATCH = false, bool EXPL = false>
 KC_D void selectBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bool loaded, bool fused,
-                     uint32_t* hasBits, float* rootPol) {
+                     uint32_t* hasBits, float* rootPol, int row = -1) {
   GV v(d, T, g);
+  if(row >= 0)  // a wide engine's rows: the slot's first
+    v.row = row;
   SPROF_INIT();
   const unsigned long long t0 = SPROF_NOW();
   if(d.nnDefer[g]) {
     // the leaf from an earlier round still waits for the network (kCompact); the
     // game state stays as it is
     if(v.lane == 0)
-      d.nnNeed[g] = 1;
+      d.nnNeed[v.row] = 1;
     return;
   }
   if(loaded)
@@ -1419,14 +1517,14 @@ KC_D void selectBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
         s.startDelay = s.startDelay - 1;
       storeGame(v, s);
       if(v.lane == 0)
-        d.nnNeed[g] = 0;
+        d.nnNeed[v.row] = 0;
       return;
     }
     if(v.lane == 0) {
       d.games[g].leafKind = LEAF_NONE;
       if(s.startDelay > 0)
         d.games[g].startDelay = s.startDelay - 1;
-      d.nnNeed[g] = 0;
+      d.nnNeed[v.row] = 0;
     }
     return;
   }
@@ -1842,8 +1940,9 @@ KC_D const T* uniformConst(const T* p) {
 }
 // (EXPL: nothing here reads it; it gives each round kernel the out-of-line copy of its own
 // instantiation family, as MATCH does, so a copy's callers -- and with them what the compiler
-// propagates into it -- stay the ones it had before the exploration kernels existed)
-template <int NI, bool MATCH = false, bool EXPL = false>
+// propagates into it -- stay the ones it had before the exploration kernels existed; WIDE likewise
+// for the wide kernels)
+template <int NI, bool MATCH = false, bool EXPL = false, bool WIDE = false>
 __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, int g, GameDev* gs, float* scratch) {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   const SearchDev& d = *uniformConst(dp);
@@ -1938,11 +2037,119 @@ __device__ __noinline__ bool rareLeaf(const SearchDev* dp, const DTables* Tp, in
   return needCommit;
 }
 
+// One playout's backup: the leaf takes its evaluation (post-processed from the playout's network
+// row, or the cache hit's) or its terminal / repeated value, and the path is backed up.
+// The NN-cache slot the evaluation bid for is written by the round's highest bidding row.
+// P, o: d.P and the playout's network output row (the caller has both at hand).
+template <int NI, bool MATCH = false, bool EXPL = false>
+KC_D void playoutBackup(const GV& v, GameDev& s, const int P, const float* o, bool fused, float* scratch) {
+  const SearchDev& d = v.d;
+  const int g = v.g;
+  unsigned long long tPost = 0, tLeaf = 0, tPath = 0;
+  (void)tPost;
+  (void)tLeaf;
+  (void)tPath;
+  NStats leafSt{0u, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  bool haveLeaf = false;
+  if(s.leafKind == LEAF_NN || s.leafKind == LEAF_CACHED) {
+    float w, l, err = 0.0f;  // err: the evaluation's short-term error (uncertainty weighting)
+    float* pol = v.pol(s.leafNode);
+    const unsigned long long ta = SPROF_NOW();
+    (void)ta;
+    float pv[NI];
+#ifdef KC_SEARCH_PROFILE
+    if(v.lane == 0)
+      probeLeafKey(v.nodeKey(s.leafNode)[0], v.nodeKey(s.leafNode)[1]);
+#endif
+    if(s.leafKind == LEAF_CACHED) {
+      // copied from the cache into the leaf's policy by kSelect
+#pragma unroll
+      for(int j = 0; j < NI; j++) {
+        const int pos = v.lane + 64 * j;
+        pv[j] = pos < P ? pol[pos] : -1.0f;
+      }
+      w = s.cHitWin;
+      l = s.cHitLoss;
+      err = s.cHitErr;
+    } else {
+      float st;
+      postprocess<NI>(v, s.leaf, s.leafSym, o, pol, w, l, st, scratch, pv);
+      // MATCH with a shared net: the cache entry written below serves both sides, so it carries the
+      // error whenever either side weights by it (the side with the setting off ignores it:
+      // uncWeightOf gives 1)
+      bool wantErr = v.unc->on != 0;
+      if constexpr(MATCH)
+        wantErr = wantErr || (d.matchSharedNet && (d.unc.on | d.unc1.on) != 0);
+      if(wantErr)
+        err = stErrorOf(st);
+      if(d.cacheOn) {
+        // kCompact bid this evaluation for the state's cache slot (atomicMax of
+        // game + 1 over the round's batch); the highest bidder stores its payload
+        // and clears the tag, deterministic whatever the block order.  Nothing
+        // reads the table in this kernel (hits were copied by kSelect).
+        const NNCache c = cacheOf<MATCH>(d, MATCH ? netOf(d, g, s) : 0);
+        const uint32_t slot = (uint32_t)s.cSlot;
+        if(c.tag[slot] == (uint32_t)v.row + 1u) {
+          float* cp = c.pol + (size_t)slot * P;
+#pragma unroll
+          for(int j = 0; j < NI; j++)
+            if(v.lane + 64 * j < P)
+              cp[v.lane + 64 * j] = pv[j];
+          if(v.lane == 0) {
+            c.val[2 * (size_t)slot] = w;
+            c.val[2 * (size_t)slot + 1] = l;
+            c.err[slot] = err;
+            c.key[2 * (size_t)slot] = v.nodeKey(s.leafNode)[0];
+            c.key[2 * (size_t)slot + 1] = v.nodeKey(s.leafNode)[1];
+            if(fused)
+              d.cClear[g] = slot + 1u;
+            else
+              c.tag[slot] = 0;
+          }
+        }
+      }
+    }
+    firstExpansion<NI>(v, s.leafNode, pv);
+    const float weight = uncWeightOf(*v.unc, err);
+    if(v.lane == 0) {
+      Node* n = &v.nodes()[s.leafNode];
+      n->nnWin = w;
+      n->nnLoss = l;
+      n->nnWeight = weight;
+      n->flags |= 1;
+    }
+    waveSync();
+    const unsigned long long tb = SPROF_NOW();
+    (void)tb;
+    leafSt = addLeafValue(v, s, s.leafNode, w - l, weight, false, true);
+    haveLeaf = true;
+    tPost = tb - ta;
+    tLeaf = SPROF_NOW() - tb;
+  } else if(s.leafKind == LEAF_TERMINAL) {
+    float val = s.leaf.winner == 2 ? 1.0f : (s.leaf.winner == 1 ? -1.0f : 0.0f);
+    leafSt = addLeafValue(v, s, s.leafNode, val, uncTerminalWeight(*v.unc), true, false);
+    haveLeaf = true;
+  } else if(s.leafKind == LEAF_NOCHILD) {
+    const Node& n = v.nodes()[s.leafNode];
+    leafSt = addLeafValue(v, s, s.leafNode, n.nnWin - n.nnLoss, n.nnWeight, false, false);
+    haveLeaf = true;
+  }
+  const unsigned long long tp0 = SPROF_NOW();
+  (void)tp0;
+  // an updated leaf is the deepest level's path child (a catch-up leaf is unchanged)
+  backupPath<NI, EXPL>(v, s, s.pathLen, leafSt, haveLeaf);
+  tPath = SPROF_NOW() - tp0;
+  s.playouts++;
+  SPROF_ADD(12, tPost);
+  SPROF_ADD(13, tPath);
+  SPROF_ADD(14, tLeaf);
+}
+
 // One game's backup; returns whether s holds the game's state afterwards (fused: not yet
 // stored -- selectBody stores it on every path).
 // fused (kBackupSelect): a cache-slot winner leaves the slot's tag set -- the selections
 // running beside it treat the slot as being written -- and kResolve clears it.
-template <int NI, bool MATCH = false, bool EXPL = false>
+template <int NI, bool MATCH = false, bool EXPL = false, bool WIDE = false>
 KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bool fused, float* scratch) {
   if(d.nnDefer[g])  // a deferred leaf is backed up in a later round
     return false;
@@ -1953,107 +2160,13 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   loadGame<MATCH>(v, s);
   if(s.leafKind == LEAF_NONE)
     return true;
-  unsigned long long tPost = 0, tLeaf = 0, tPath = 0;
-  (void)tPost;
-  (void)tLeaf;
-  (void)tPath;
   const int P = d.P;
   const float* o = d.nnOut + (size_t)s.nnSlot * (P + 4);
   bool needCommit = false;
   if(s.leafKind == LEAF_INIT || s.leafKind == LEAF_FORK || s.leafKind == LEAF_SIDE || s.leafKind == LEAF_ROOTEVAL) {
-    needCommit = rareLeaf<NI, MATCH, EXPL>(&d, &T, g, &s, scratch);
+    needCommit = rareLeaf<NI, MATCH, EXPL, WIDE>(&d, &T, g, &s, scratch);
   } else {
-    NStats leafSt{0u, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    bool haveLeaf = false;
-    if(s.leafKind == LEAF_NN || s.leafKind == LEAF_CACHED) {
-      float w, l, err = 0.0f;  // err: the evaluation's short-term error (uncertainty weighting)
-      float* pol = v.pol(s.leafNode);
-      const unsigned long long ta = SPROF_NOW();
-      (void)ta;
-      float pv[NI];
-#ifdef KC_SEARCH_PROFILE
-      if(v.lane == 0)
-        probeLeafKey(v.nodeKey(s.leafNode)[0], v.nodeKey(s.leafNode)[1]);
-#endif
-      if(s.leafKind == LEAF_CACHED) {
-        // copied from the cache into the leaf's policy by kSelect
-#pragma unroll
-        for(int j = 0; j < NI; j++) {
-          const int pos = v.lane + 64 * j;
-          pv[j] = pos < P ? pol[pos] : -1.0f;
-        }
-        w = s.cHitWin;
-        l = s.cHitLoss;
-        err = s.cHitErr;
-      } else {
-        float st;
-        postprocess<NI>(v, s.leaf, s.leafSym, o, pol, w, l, st, scratch, pv);
-        // MATCH with a shared net: the cache entry written below serves both sides, so it carries the
-        // error whenever either side weights by it (the side with the setting off ignores it:
-        // uncWeightOf gives 1)
-        bool wantErr = v.unc->on != 0;
-        if constexpr(MATCH)
-          wantErr = wantErr || (d.matchSharedNet && (d.unc.on | d.unc1.on) != 0);
-        if(wantErr)
-          err = stErrorOf(st);
-        if(d.cacheOn) {
-          // kCompact bid this evaluation for the state's cache slot (atomicMax of
-          // game + 1 over the round's batch); the highest bidder stores its payload
-          // and clears the tag, deterministic whatever the block order.  Nothing
-          // reads the table in this kernel (hits were copied by kSelect).
-          const NNCache c = cacheOf<MATCH>(d, MATCH ? netOf(d, g, s) : 0);
-          const uint32_t slot = (uint32_t)s.cSlot;
-          if(c.tag[slot] == (uint32_t)g + 1u) {
-            float* cp = c.pol + (size_t)slot * P;
-#pragma unroll
-            for(int j = 0; j < NI; j++)
-              if(v.lane + 64 * j < P)
-                cp[v.lane + 64 * j] = pv[j];
-            if(v.lane == 0) {
-              c.val[2 * (size_t)slot] = w;
-              c.val[2 * (size_t)slot + 1] = l;
-              c.err[slot] = err;
-              c.key[2 * (size_t)slot] = v.nodeKey(s.leafNode)[0];
-              c.key[2 * (size_t)slot + 1] = v.nodeKey(s.leafNode)[1];
-              if(fused)
-                d.cClear[g] = slot + 1u;
-              else
-                c.tag[slot] = 0;
-            }
-          }
-        }
-      }
-      firstExpansion<NI>(v, s.leafNode, pv);
-      const float weight = uncWeightOf(*v.unc, err);
-      if(v.lane == 0) {
-        Node* n = &v.nodes()[s.leafNode];
-        n->nnWin = w;
-        n->nnLoss = l;
-        n->nnWeight = weight;
-        n->flags |= 1;
-      }
-      waveSync();
-      const unsigned long long tb = SPROF_NOW();
-      (void)tb;
-      leafSt = addLeafValue(v, s, s.leafNode, w - l, weight, false, true);
-      haveLeaf = true;
-      tPost = tb - ta;
-      tLeaf = SPROF_NOW() - tb;
-    } else if(s.leafKind == LEAF_TERMINAL) {
-      float val = s.leaf.winner == 2 ? 1.0f : (s.leaf.winner == 1 ? -1.0f : 0.0f);
-      leafSt = addLeafValue(v, s, s.leafNode, val, uncTerminalWeight(*v.unc), true, false);
-      haveLeaf = true;
-    } else if(s.leafKind == LEAF_NOCHILD) {
-      const Node& n = v.nodes()[s.leafNode];
-      leafSt = addLeafValue(v, s, s.leafNode, n.nnWin - n.nnLoss, n.nnWeight, false, false);
-      haveLeaf = true;
-    }
-    const unsigned long long tp0 = SPROF_NOW();
-    (void)tp0;
-    // an updated leaf is the deepest level's path child (a catch-up leaf is unchanged)
-    backupPath<NI, EXPL>(v, s, s.pathLen, leafSt, haveLeaf);
-    tPath = SPROF_NOW() - tp0;
-    s.playouts++;
+    playoutBackup<NI, MATCH, EXPL>(v, s, P, o, fused, scratch);
     needCommit = v.nodes()[s.rootIdx].visits >= (uint32_t)s.visitLimit;
   }
   if(needCommit) {
@@ -2068,9 +2181,6 @@ KC_D bool backupBody(const SearchDev& d, const DTables& T, int g, GameDev& s, bo
   SPROF_ADD(10, 1);
   SPROF_MAX(26, SPROF_NOW() - t0);
   SPROF_ADD(11, SPROF_NOW() - t0);
-  SPROF_ADD(12, tPost);
-  SPROF_ADD(13, tPath);
-  SPROF_ADD(14, tLeaf);
   SPROF_FLUSH();
   return true;
 }
@@ -2112,6 +2222,206 @@ __global__ void __launch_bounds__(64, NI <= 2 ? 4 : 2) kBackupSelect(const Searc
   const bool loaded = backupBody<NI, false, EXPL>(d, T, g, s, true, scratch);
   // (the selection's root policy reuses the backup's scratch)
   selectBody<NI, false, EXPL>(d, T, g, s, loaded, true, hasBits, scratch);
+}
+
+// ---------------------------------------------------------------------------
+// Parallel playouts per search (coffee_analysis_set_search_threads).  With
+// wideK = K a searching slot makes up to K descents a round, one after the other on its one
+// wave, steered apart by virtual losses (vloss.h); their leaves go through the network in the
+// round's one batch, descent j of slot g on row g K + j, and the backups then run in the same
+// order.  Between the two kernels descent j's leaf lives in wideRec[g][j] and its path in
+// widePathNode / widePathSlot [g][j].  Every other phase runs the single-playout code on the
+// slot's first row.
+static_assert(sizeof(DBoard) % 4 == 0, "DBoard copy granularity");
+KC_D void saveLeaf(const GV& v, const GameDev& s, WideRec* r) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(&s.leaf);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(&r->leaf);
+  for(int i = v.lane; i < (int)(sizeof(DBoard) / 4); i += 64)
+    dst[i] = src[i];
+  if(v.lane == 0) {
+    r->leafKind = s.leafKind;
+    r->leafNode = s.leafNode;
+    r->leafSym = s.leafSym;
+    r->nnSlot = s.nnSlot;
+    r->cSlot = s.cSlot;
+    r->pathLen = s.pathLen;
+    r->cHitWin = s.cHitWin;
+    r->cHitLoss = s.cHitLoss;
+    r->cHitErr = s.cHitErr;
+  }
+}
+KC_D void loadLeaf(const GV& v, GameDev& s, const WideRec* r) {
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(&r->leaf);
+  uint32_t* dst = reinterpret_cast<uint32_t*>(&s.leaf);
+  for(int i = v.lane; i < (int)(sizeof(DBoard) / 4); i += 64)
+    dst[i] = src[i];
+  s.leafKind = r->leafKind;
+  s.leafNode = r->leafNode;
+  s.leafSym = r->leafSym;
+  s.nnSlot = r->nnSlot;
+  s.cSlot = r->cSlot;
+  s.pathLen = r->pathLen;
+  s.cHitWin = r->cHitWin;
+  s.cHitLoss = r->cHitLoss;
+  s.cHitErr = r->cHitErr;
+  waveSync();
+}
+
+template <int NI, bool EXPL = false>
+__global__ void __launch_bounds__(64, NI <= 2 ? 4 : 2) kSelectWide(const SearchDev* __restrict__ dp,
+                                                                    const DTables* __restrict__ Tp, int resetCommit) {
+  const SearchDev& d = *dp;
+  const int g = blockIdx.x;
+  if(resetCommit && g == 0 && threadIdx.x == 0)
+    *d.commitCount = 0;
+  if(g >= d.G)
+    return;
+  __shared__ uint32_t hasBits[(MAX_P + 31) / 32];
+  __shared__ GameDev s;
+  __shared__ float rootPol[MAX_P];
+  const int K = d.wideK, lane = laneId();
+  if(lane < K)
+    d.nnNeed[g * K + lane] = 0;
+  const int phase = __builtin_amdgcn_readfirstlane(d.games[g].phase);
+  if(phase != PH_SEARCH) {
+    if(lane == 0)
+      d.wideCount[g] = 0;
+    if(phase == PH_COMMIT) {  // idle, or waiting for its report
+      if(lane == 0)
+        d.games[g].leafKind = LEAF_NONE;
+      return;
+    }
+    selectBody<NI, false, EXPL>(d, *Tp, g, s, false, false, hasBits, rootPol, g * K);
+    return;
+  }
+  GV v(d, *Tp, g);
+  loadGame(v, s);
+  DRng rng = DRng{s.rngSeed, s.rngCtr};
+  // never past the visit limit: every descent that does not collide adds one root visit
+  const int left = s.visitLimit - (int)v.nodes()[s.rootIdx].visits;
+  const int n = left < K ? left : K;
+  int made = 0;
+  bool collided = false;
+  for(int j = 0; j < n && !collided; j++) {
+    v.setDescent(j);
+    descend<NI, EXPL, true>(v, s, hasBits, rootPol, j == 0);
+    made = j + 1;
+    collided = s.leafKind == LEAF_COLLISION;
+    if(collided) {
+      removeVirtualLosses(v, s.pathLen, s.leafNode);
+    } else {
+      if(s.leafKind == LEAF_NN && d.cacheOn)
+        cacheLookup<NI>(v, s, false);
+      finishLeaf<W1_OF<NI>>(v, s, rng);
+    }
+    waveSync();
+    saveLeaf(v, s, d.wideRec + v.row);
+    waveSync();
+  }
+  s.leafKind = LEAF_WIDE;
+  if(lane == 0) {
+    d.wideCount[g] = made;
+    atomicAdd(&d.wideCtr[WC_DESCENTS], (unsigned long long)made);
+    if(collided)
+      atomicAdd(&d.wideCtr[WC_COLLISIONS], 1ull);
+  }
+  waveSync();
+  storeGame(v, s);
+}
+
+template <int NI, bool EXPL = false>
+__global__ void __launch_bounds__(64, NI <= 4 ? 4 : 3) kBackupWide(const SearchDev* __restrict__ dp,
+                                                                    const DTables* __restrict__ Tp) {
+  const SearchDev& d = *uniformConst(dp);  // constant views: see kBackup
+  const DTables& T = *uniformConst(Tp);
+  const int g = blockIdx.x;
+  if(g >= d.G)
+    return;
+  __shared__ __attribute__((aligned(16))) float scratch[3 * MAX_P];
+  __shared__ GameDev s;
+  if(__builtin_amdgcn_readfirstlane(d.games[g].leafKind) != LEAF_WIDE) {
+    backupBody<NI, false, EXPL, true>(d, T, g, s, false, scratch);
+    return;
+  }
+  GV v(d, T, g);
+  loadGame(v, s);
+  const int made = __builtin_amdgcn_readfirstlane(d.wideCount[g]);
+  for(int j = 0; j < made; j++) {
+    v.setDescent(j);
+    loadLeaf(v, s, d.wideRec + v.row);
+    if(s.leafKind == LEAF_COLLISION)  // the round's last: its virtual losses came off in the selection
+      break;
+    playoutBackup<NI, false, EXPL>(v, s, d.P, d.nnOut + (size_t)s.nnSlot * (d.P + 4), false, scratch);
+    removeVirtualLosses(v, s.pathLen, s.leafNode);
+  }
+  // the commit test once, after the last backup
+  if(v.nodes()[s.rootIdx].visits >= (uint32_t)s.visitLimit) {
+    s.phase = PH_COMMIT;
+    if(v.lane == 0)
+      d.commitList[atomicAdd(d.commitCount, 1)] = g;
+  }
+  s.leafKind = LEAF_NONE;
+  waveSync();
+  storeGame(v, s);
+}
+
+// The batch of a wide round: the rows that need the network in ascending order, and each one's bid
+// for its NN-cache slot (the highest row stores, as the highest game does in kCompact).  One
+// workgroup; a wide engine's rows never exceed its batch cap (coffee_analysis_set_search_threads),
+// so no row is deferred.
+__global__ void __launch_bounds__(1024) kCompactWide(const SearchDev* __restrict__ dp, int accumulate) {
+  const SearchDev& d = *dp;
+  __shared__ int wsum[16];
+  const int nt = blockDim.x, nw = nt >> 6;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int R = d.G * d.wideK;
+  const uint64_t below = (1ull << lane) - 1ull;
+  int base = 0;  // rows listed by the chunks before (uniform)
+  for(int c0 = 0; c0 < R; c0 += nt) {
+    const int i = c0 + t;
+    const bool nd = i < R && d.nnNeed[i] != 0;
+    const uint64_t b = ballot(nd);
+    if(lane == 0)
+      wsum[w] = __popcll(b);
+    __syncthreads();
+    int off = base, tot = 0;
+    for(int q = 0; q < nw; q++) {
+      off += q < w ? wsum[q] : 0;
+      tot += wsum[q];
+    }
+    if(nd) {
+      d.nnIdx[off + __popcll(b & below)] = i;
+      const uint32_t bid = d.nnBid[i];
+      if(bid != ~0u)
+        atomicMax(&d.cTag[bid], (uint32_t)i + 1u);
+    }
+    base += tot;
+    __syncthreads();
+  }
+  if(t == 0) {
+    *d.nnCount = base;
+    *d.pendCount = 0;
+    if(accumulate)
+      *d.nnTimedEvals += (unsigned long long)base;
+  }
+}
+
+// The virtual losses live in the engine's trees (0 between rounds): one wave per slot over the
+// slot's allocated nodes.
+__global__ void __launch_bounds__(64) kVirtualLossCount(const SearchDev* __restrict__ dp, unsigned long long* out) {
+  const SearchDev& d = *dp;
+  const int g = blockIdx.x, lane = laneId();
+  const Node* NS = d.nodes + (size_t)g * d.cap;
+  const uint32_t* bits = d.allocBits + (size_t)g * (d.cap / 32);
+  int sum = 0;
+  for(int i = lane; i < d.cap; i += 64)
+    if((bits[i >> 5] >> (i & 31)) & 1u)
+      sum += NS[i].virtualLosses;
+#pragma unroll
+  for(int off = 32; off >= 1; off >>= 1)
+    sum += __shfl_xor(sum, off, 64);
+  if(lane == 0 && sum != 0)
+    atomicAdd(out, (unsigned long long)sum);
 }
 
 #ifdef KC_SEARCH_PROFILE
@@ -4896,7 +5206,9 @@ void launchCompact(const SearchDev& d, const SearchDev* dd, hipStream_t st, bool
   const int nt = d.G <= 4 * 64 * CP_CH ? 256 : 1024;  // 1024 only past 8192 games per engine
   const DTables* T = d.T;
   const int a = accumulate ? 1 : 0;
-  if(d.matchMode)
+  if(d.wideK > 1)
+    hipLaunchKernelGGL(kCompactWide, dim3(1), dim3(d.G * d.wideK <= 256 ? 256 : 1024), 0, st, dd, a);
+  else if(d.matchMode)
     hipLaunchKernelGGL((kCompact<2, false, true>), dim3(1), dim3(nt), 0, st, dd, T, a);
   else if(!resolve)
     hipLaunchKernelGGL((kCompact<2, false>), dim3(1), dim3(nt), 0, st, dd, T, a);
@@ -4925,6 +5237,15 @@ static bool explLaunch(const SearchDev& d) {
 void launchSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEvent_t e0, hipEvent_t e1,
                   bool resetCommit) {
   const int rc = resetCommit ? 1 : 0;
+  if(d.wideK > 1) {  // parallel playouts: an analysis engine's setting
+    byItems(d.P, [&](auto ni) {
+      byFlag(explLaunch(d), [&](auto e) {
+        launchEv(kSelectWide<ni(), e()>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, d.T, rc);
+      });
+    });
+    KC_HIP(hipGetLastError());
+    return;
+  }
   byItems(d.P, [&](auto ni) {
     byFlag(d.matchMode, [&](auto m) {
       byFlag(explLaunch(d), [&](auto e) {
@@ -4936,6 +5257,15 @@ void launchSelect(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEv
 }
 
 void launchBackup(const SearchDev& d, const SearchDev* dd, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  if(d.wideK > 1) {
+    byItems(d.P, [&](auto ni) {
+      byFlag(explLaunch(d), [&](auto e) {
+        launchEv(kBackupWide<ni(), e()>, dim3(d.G), dim3(64), 0, st, e0, e1, dd, d.T);
+      });
+    });
+    KC_HIP(hipGetLastError());
+    return;
+  }
   byItems(d.P, [&](auto ni) {
     byFlag(d.matchMode, [&](auto m) {
       byFlag(explLaunch(d), [&](auto e) {
@@ -4992,6 +5322,12 @@ void launchCommit(const SearchDev& d, const SearchDev* dd, hipStream_t st) {
     hipLaunchKernelGGL(kStartPosTurns, dim3(d.G), dim3(64), 0, st, dd, d.T);
     KC_HIP(hipGetLastError());
   }
+}
+
+void launchVirtualLossCount(const SearchDev& d, const SearchDev* dd, unsigned long long* out, hipStream_t st) {
+  KC_HIP(hipMemsetAsync(out, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(kVirtualLossCount, dim3(d.G), dim3(64), 0, st, dd, out);
+  KC_HIP(hipGetLastError());
 }
 
 void launchGameTree(const SearchDev* dd, int slot, int maxNodes, uint32_t* nodesOut, uint32_t* edgesOut,

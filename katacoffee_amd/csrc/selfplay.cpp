@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <cstring>
 
 namespace kc {
@@ -490,6 +491,7 @@ SelfplayEngine::SelfplayEngine(const coffee_selfplay_config& c, const char* cons
   }
   d.nnCap = nnCapFor(G);
   d.nnIdx = devAlloc<int32_t>(owned_, G);
+  rowsAllocated_ = (size_t)G;
   d.modelGen = devAlloc<int32_t>(owned_, 1);
   d.nnCount = devAlloc<int32_t>(owned_, 1);
   if(c.nn_cache_log2 < 0 || c.nn_cache_log2 > 26)
@@ -646,7 +648,8 @@ void SelfplayEngine::resolveTiming() {
 }
 
 bool SelfplayEngine::fuseNow() const {
-  if(hd_.matchMode)  // match play always runs the separate select and backup kernels
+  // match play and parallel playouts always run the separate select and backup kernels
+  if(hd_.matchMode || hd_.wideK > 1)
     return false;
   if(fuseRounds_ >= 0)
     return fuseRounds_ == 1;
@@ -938,7 +941,7 @@ void SelfplayEngine::forwardNet(int n, const int32_t* count, const int32_t* idx,
                                 hipEvent_t b) {
   const SearchDev& d = hd_;
   Net& net = nets_[n];
-  const int rows = std::min(d.G, d.nnCap);  // grid bound; the batch is *count rows
+  const int rows = std::min(this->rows(), d.nnCap);  // grid bound; the batch is *count rows
   if(net.nn) {
     net.nn->forward(rows, d.nnIn, d.nnOut, st, count, idx, a, b);
   } else {
@@ -976,7 +979,7 @@ void SelfplayEngine::auditCheck() {
       // the same model on the accurate instance from here on (this net's cached evaluations cleared)
       net.nn.reset(new NNEngine(*net.model, xLen_, yLen_, winLen_, NN_ACCURATE));
       net.auditSwitches++;
-      const int cap = nnCapFor(hd_.G);
+      const int cap = nnCapFor(rows());
       if(cap != hd_.nnCap) {
         hd_.nnCap = cap;
         KC_HIP(hipMemcpy(&dd_->nnCap, &cap, sizeof(int), hipMemcpyHostToDevice));
@@ -1147,6 +1150,127 @@ int SelfplayEngine::analysisDrain(int max, coffee_analysis_result* header, coffe
   return n;
 }
 
+void SelfplayEngine::setSearchThreads(int threads, float perThread) {
+  if(!hd_.analysisMode)
+    throw std::invalid_argument("not an analysis engine");
+  if(threads < 1 || threads > MAX_SEARCH_THREADS)
+    throw std::invalid_argument("set_search_threads: threads must be in 1.." + std::to_string(MAX_SEARCH_THREADS));
+  if(!(perThread > 0.0f) || !std::isfinite(perThread))
+    throw std::invalid_argument("set_search_threads: virtual_losses_per_thread must be finite and > 0");
+  // a tree never mixes two settings: every submitted query has its result
+  sync();
+  unsigned long long written = 0;
+  KC_HIP(hipMemcpy(&written, hd_.aCtr + AC_RESULTS, 8, hipMemcpyDeviceToHost));
+  if(written != aSubmitted_)
+    throw std::invalid_argument("set_search_threads: only while the engine holds no query");
+  // a wide round fits one network launch: no row is ever deferred
+  const size_t rows = (size_t)hd_.G * threads;
+  if(threads > 1) {
+    const int cap = nnCapFor(1 << 30);
+    if(rows > (size_t)cap)
+      throw std::invalid_argument("set_search_threads: num_slots x threads = " + std::to_string(rows) +
+                                  " exceeds the batch cap of one network launch (" + std::to_string(cap) + ")");
+  }
+  SearchDev& d = hd_;
+  if(rows > rowsAllocated_) {
+    // the network batch arrays by row; the ones they replace stay owned until the engine goes
+    d.nnIn = devAlloc<uint64_t>(owned_, rows * d.inWords);
+    d.nnOut = devAlloc<float>(owned_, rows * (d.P + 4));
+    d.nnNeed = devAlloc<int32_t>(owned_, rows);
+    d.nnBid = devAlloc<uint32_t>(owned_, rows);
+    d.nnIdx = devAlloc<int32_t>(owned_, rows);
+    for(int n = 0; n < numNets_; n++)
+      nets_[n].auditOut = devAlloc<float>(owned_, rows * (d.P + 4), false);
+    d.wideRec = devAlloc<WideRec>(owned_, rows);
+    d.widePathNode = devAlloc<int32_t>(owned_, rows * MAX_DEPTH);
+    d.widePathSlot = devAlloc<int32_t>(owned_, rows * MAX_DEPTH);
+    if(d.wideCount.p == nullptr) {
+      d.wideCount = devAlloc<int32_t>(owned_, d.G);
+      d.wideCtr = devAlloc<unsigned long long>(owned_, WC_N);
+    }
+    rowsAllocated_ = rows;
+  }
+  d.wideK = threads;
+  d.vlPerThread = perThread;
+  d.nnCap = nnCapFor((int)rows);
+  // the stream is idle (sync above): plain copies, member by member (the device copy's aPolicy
+  // may differ from the host's, setRootOptions)
+  auto up = [&](auto SearchDev::*m) {
+    KC_HIP(hipMemcpy(&(dd_->*m), &(d.*m), sizeof(d.*m), hipMemcpyHostToDevice));
+  };
+  up(&SearchDev::nnIn);
+  up(&SearchDev::nnOut);
+  up(&SearchDev::nnNeed);
+  up(&SearchDev::nnBid);
+  up(&SearchDev::nnIdx);
+  up(&SearchDev::nnCap);
+  up(&SearchDev::wideRec);
+  up(&SearchDev::widePathNode);
+  up(&SearchDev::widePathSlot);
+  up(&SearchDev::wideCount);
+  up(&SearchDev::wideCtr);
+  up(&SearchDev::wideK);
+  up(&SearchDev::vlPerThread);
+}
+
+void SelfplayEngine::searchThreadsInfo(coffee_search_threads_info& out) {
+  if(!hd_.analysisMode)
+    throw std::invalid_argument("not an analysis engine");
+  sync();
+  memset(&out, 0, sizeof(out));
+  out.threads = std::max(1, (int)hd_.wideK);
+  out.virtual_losses_per_thread = hd_.wideK >= 1 ? hd_.vlPerThread : 1.0f;
+  if(hd_.wideCtr.p != nullptr) {
+    unsigned long long c[WC_N];
+    KC_HIP(hipMemcpy(c, hd_.wideCtr, sizeof(c), hipMemcpyDeviceToHost));
+    out.descents = c[WC_DESCENTS];
+    out.collisions = c[WC_COLLISIONS];
+  }
+  if(!launchVirtualLossCount)
+    throw std::runtime_error("search_threads_info: the search kernels are not linked");
+  if(!vlCount_)
+    vlCount_ = devAlloc<unsigned long long>(owned_, 1);
+  launchVirtualLossCount(hd_, dd_, vlCount_, stream_);
+  KC_HIP(hipStreamSynchronize(stream_));
+  unsigned long long live = 0;
+  KC_HIP(hipMemcpy(&live, vlCount_, 8, hipMemcpyDeviceToHost));
+  out.live_virtual_losses = live;
+}
+
+void SelfplayEngine::roundPaths(int slot, coffee_round_paths& out) {
+  if(!hd_.analysisMode)
+    throw std::invalid_argument("not an analysis engine");
+  if(slot < 0 || slot >= hd_.G)
+    throw std::invalid_argument("slot out of range");
+  sync();
+  memset(&out, 0, sizeof(out));
+  if(hd_.wideK <= 1)
+    return;
+  const int K = hd_.wideK;
+  int32_t made = 0;
+  KC_HIP(hipMemcpy(&made, hd_.wideCount + slot, 4, hipMemcpyDeviceToHost));
+  made = std::min(std::max(made, 0), K);
+  std::vector<WideRec> rec((size_t)K);
+  std::vector<int32_t> pn((size_t)K * MAX_DEPTH), ps((size_t)K * MAX_DEPTH);
+  const size_t row0 = (size_t)slot * K;
+  KC_HIP(hipMemcpy(rec.data(), hd_.wideRec + row0, sizeof(WideRec) * K, hipMemcpyDeviceToHost));
+  KC_HIP(hipMemcpy(pn.data(), hd_.widePathNode + row0 * MAX_DEPTH, 4 * (size_t)K * MAX_DEPTH, hipMemcpyDeviceToHost));
+  KC_HIP(hipMemcpy(ps.data(), hd_.widePathSlot + row0 * MAX_DEPTH, 4 * (size_t)K * MAX_DEPTH, hipMemcpyDeviceToHost));
+  static_assert(COFFEE_ROUND_PATH_MAX == MAX_DEPTH && COFFEE_SEARCH_THREADS_MAX == MAX_SEARCH_THREADS,
+                "katacoffee.h path geometry");
+  out.num_descents = made;
+  for(int j = 0; j < made; j++) {
+    coffee_round_path& o = out.path[j];
+    o.leaf_kind = rec[j].leafKind;
+    o.path_len = std::min(std::max(rec[j].pathLen, 0), MAX_DEPTH);
+    const int n = std::min(MAX_DEPTH, o.path_len + (o.leaf_kind == LEAF_COLLISION ? 1 : 0));
+    for(int i = 0; i < n; i++) {
+      o.node[i] = pn[(size_t)j * MAX_DEPTH + i];
+      o.child_slot[i] = ps[(size_t)j * MAX_DEPTH + i];
+    }
+  }
+}
+
 void SelfplayEngine::analysisStats(coffee_analysis_stats& out) {
   if(!hd_.analysisMode)
     throw std::invalid_argument("not an analysis engine");
@@ -1309,7 +1433,7 @@ void SelfplayEngine::switchModel(const ModelHost& m) {
   nets_[0].auditSeen = 0.0f;
   KC_HIP(hipMemset(nets_[0].auditMax, 0, 4));
   // a reload may change the network path (fused <-> layered) and with it the default cap
-  const int cap = nnCapFor(hd_.G);
+  const int cap = nnCapFor(rows());
   if(cap != hd_.nnCap) {
     hd_.nnCap = cap;
     KC_HIP(hipMemcpy(&dd_->nnCap, &cap, sizeof(int), hipMemcpyHostToDevice));

@@ -87,6 +87,12 @@ class SelfplayEngine {
   // Root restrictions: only before the first submitted query.
   void setRootOptions(const coffee_analysis_root_options& o);
   void analysisStats(coffee_analysis_stats& out);
+  // Parallel playouts per search: only while the engine holds no query.  Throws
+  // std::invalid_argument, the engine untouched, for a value out of range or num_slots x threads
+  // past the batch cap of one network launch.
+  void setSearchThreads(int threads, float perThread);
+  void searchThreadsInfo(coffee_search_threads_info& out);
+  void roundPaths(int slot, coffee_round_paths& out);
   int drain(int maxRows, uint8_t* bin, float* glob, int16_t* pol, float* gt, int8_t* val, int32_t* meta);
   // header [g][4]; match mode [g][5], the candidate's colour last
   int drainGames(int maxGames, int32_t* header, uint8_t* moves);
@@ -161,6 +167,10 @@ class SelfplayEngine {
   int enginesPerDevice_ = 1; // engines sharing the device's default fused batch cap
   int cus_ = 1;              // compute units of the device
   int nnCapFor(int G) const;
+  // network rows of a round: one per slot, or with parallel playouts one per slot and descent
+  int rows() const { return hd_.G * std::max(1, (int)hd_.wideK); }
+  size_t rowsAllocated_ = 0;                  // rows the network batch arrays hold
+  unsigned long long* vlCount_ = nullptr;     // device: launchVirtualLossCount's sum
   int32_t modelGen_ = 0;  // hot reloads so far
   uint64_t rounds_ = 0;
   bool commitReset_ = false;  // a commit ran: the next kSelect zeroes the commit count

@@ -4,6 +4,7 @@
   python tools/analysis_bench.py [--arch b6c96] [--slots 4096] [--visits 500] [--rounds 2000]
                                  [--warmup 1000] [--precision default] [--repeats 3]
                                  [--root-symmetry-pruning]
+  python tools/analysis_bench.py --queries 1 --slots 1 --visits 1600 --search-threads 1,16 [--step 4]
 
 A kc.Analysis engine is kept fed with queries (random legal openings of 0..8 moves, made with
 the device rules) so that its ring never runs dry; a kc.Selfplay engine with the same net,
@@ -16,7 +17,16 @@ playouts per second should agree; a gap means idle slots or a refill stall.
 --root-symmetry-pruning turns the analysis engine's root symmetry pruning on (DESIGN.md 8f);
 with or without it the line also carries the drained results' mean root children and mean
 principal-variation length and, where the library reports them, the share of results whose
-used symmetry group was not trivial."""
+used symmetry group was not trivial.
+
+--queries N is the latency mode: N queries are submitted at once to an engine of
+--slots slots and the time to the last answer is taken, `repeats` times on fresh positions after
+one untimed set, for each value of --search-threads (parallel playouts per search,
+set_search_threads) in turn, each on an engine of its own (an empty NN cache) and on the same
+positions.  One JSON line per value: seconds to the last
+answer, playouts per second, collisions per descent, mean root children and mean principal-
+variation length.  A library without the setting (an earlier build run as an A/B reference
+through KATACOFFEE_LIB) takes --search-threads 1 only."""
 import argparse
 import json
 import os
@@ -56,6 +66,57 @@ def openings(n, max_moves, seed):
     return lists
 
 
+def latency(a, path, search, pool):
+    """The latency mode: time to the last answer of a.queries queries, per --search-threads value.
+    Every value gets an engine of its own (an empty NN cache) and the same positions."""
+    has = hasattr(kc.lib(), "coffee_virtual_loss")
+    for K in [int(k) for k in a.search_threads.split(",")]:
+        an = kc.Analysis(X, Y, W, num_slots=a.slots, model_path=path, search=search, seed=7, commit_interval=a.step,
+                         query_capacity=max(4 * a.slots, a.queries), nn_cache_log2=a.cache_log2,
+                         nn_precision=a.precision)
+        next_id = 0
+        if has:
+            an.set_search_threads(K, a.virtual_losses_per_thread)
+        elif K != 1:
+            raise SystemExit("this library has no search threads")
+        secs, playouts, children, pv, pv_n = [], 0, 0, 0, 0
+        i0 = an.search_threads_info() if has else None
+        for rep in range(a.repeats + 1):
+            qs = [dict(id=next_id + i, moves=pool[(next_id + i) % len(pool)]) for i in range(a.queries)]
+            next_id += a.queries
+            s0 = an.stats()
+            t0 = time.perf_counter()
+            assert an.submit(qs) == len(qs)
+            got = 0
+            while got < len(qs):
+                an.step(a.step)
+                h, m = an.drain()
+                got += len(h)
+                if rep > 0 and len(h):
+                    assert np.all(h["status"] == 0) and np.all(h["visits"] == a.visits)
+                    valid = np.arange(m.shape[1])[None, :] < h["num_children"][:, None]
+                    children += int(h["num_children"].sum())
+                    pv += int(m["pv_len"][valid].sum())
+                    pv_n += int(valid.sum())
+            dt = time.perf_counter() - t0
+            if rep > 0:  # (the first set is the warm-up)
+                secs.append(dt)
+                playouts += an.stats()["playouts"] - s0["playouts"]
+            elif has:
+                i0 = an.search_threads_info()
+        i1 = an.search_threads_info() if has else None
+        print(json.dumps({
+            "mode": "latency", "arch": a.arch, "geometry": [X, Y, W], "slots": a.slots, "queries": a.queries,
+            "visits": a.visits, "precision": a.precision, "search_threads": K, "step": a.step,
+            "seconds_to_last_answer": [round(x, 5) for x in secs],
+            "playouts_per_s": round(playouts / sum(secs), 0),
+            "collisions_per_descent": round((i1["collisions"] - i0["collisions"]) /
+                                            max(i1["descents"] - i0["descents"], 1), 5) if has and K > 1 else 0.0,
+            "mean_root_children": round(children / (a.repeats * a.queries), 2),
+            "mean_pv_len": round(pv / max(pv_n, 1), 3)}), flush=True)
+        an.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", default="b6c96")
@@ -76,12 +137,20 @@ def main():
                     help="wide root noise 0.04 and futile-visit pruning at threshold 0.15 (set_root_search) in both engines")
     ap.add_argument("--root-symmetry-pruning", action="store_true",
                     help="root symmetry pruning on in the analysis engine")
+    ap.add_argument("--queries", type=int, default=0,
+                    help="latency mode: the time to the last answer of this many queries submitted at once")
+    ap.add_argument("--search-threads", default="1",
+                    help="latency mode: parallel playouts per search, a comma-separated list measured in turn")
+    ap.add_argument("--virtual-losses-per-thread", type=float, default=1.0)
     a = ap.parse_args()
     search = kc.default_analysis_params(max_visits=a.visits)
     pool = openings(8192, 8, 5)
     with tempfile.TemporaryDirectory() as td:
         path = os.path.join(td, "%s.cfnn" % a.arch)
         kc.write_random_model(a.arch, 1000, path)
+        if a.queries > 0:
+            latency(a, path, search, pool)
+            return
         common = dict(seed=7, commit_interval=16, nn_cache_log2=a.cache_log2, nn_precision=a.precision)
         an = kc.Analysis(X, Y, W, num_slots=a.slots, model_path=path, search=search, query_capacity=4 * a.slots,
                          **common)
